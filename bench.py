@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: utterances/sec of the full ESPnet2 Conformer CTC/attention training step.
 
-    python bench.py [--gpus N --steps K --warmup W --batch B]
+    python bench.py [--gpus N --steps K --warmup W --batch B] [--dump-outputs DIR] [--full]
     (N>1: either launched by the caller, python -m torch.distributed.run --nproc-per-node N ...
     bench.py --gpus N ..., or started plainly: bench.py then launches the N ranks itself, one
     process per GPU over RCCL, as espnet2/tasks/abs_task.py:1049-1070 spawns its DDP workers)
@@ -12,9 +12,12 @@ Transformer decoder 6 x (4 heads, FF 2048), V=600, ctc_weight 0.3, lsm 0.1, drop
 everywhere (SLURP YAML), SpecAug on (time warp 5, 2 freq masks <30, 2 time masks <40),
 UtteranceMVN, Adam + WarmupLR(25k) + grad clip 5.  A step = fwd + bwd + RCCL grad average
 (N>1) + clip + Adam + LR step, on a resident synthetic batch per GPU (weak scaling).
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel family (the MFMA
-GEMM) measured live with HIP events, and a CPU baseline (the oracle restatement timed on
-the host cores, rank 0 at N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes the
+last timed step's outputs (--dump-outputs) and prints the line; its roofline, attention_roofline,
+cpu_baseline and data_feed entries are null.  --full adds the legs that take runs of their own:
+the roofline of the dominant kernel family (the MFMA GEMM) and of the rel-pos attention kernel
+measured live with HIP events, the data-feed rate, and a CPU baseline (the oracle restatement
+timed on the host cores, rank 0 at N=1 only).
 """
 import argparse
 import json
@@ -257,6 +260,35 @@ def data_feed_rate(trainer, utts, steps, world):
     return world * len(utts) * steps / float(el.item())
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of a flat buffer larger than this (16 MiB of float32 each)
+
+
+def snapshot_outputs(stats, model, opt):
+    """What a caller of the timed path holds after its last step, cloned on the device right after
+    the timed region (the graph's static outputs are overwritten by any later step): every entry of
+    the stats dict train_one_step returned, and the state the step updated -- the flat fp32
+    parameters and Adam's first moment (the running gradient).  A flat buffer of more than
+    DUMP_SAMPLE elements is cut to a fixed sample: DUMP_SAMPLE sorted indices drawn once from a
+    seeded host generator, the same for every run of the same model shape."""
+    out = {k: v.detach().reshape(-1).to(torch.float32).clone() for k, v in stats.items() if torch.is_tensor(v)}
+    flat = model.flat.flat
+    idx = None
+    if flat.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(20240)
+        idx = torch.sort(torch.randperm(flat.numel(), generator=g)[:DUMP_SAMPLE])[0].to(flat.device)
+    for name, buf in (("params", flat), ("adam_exp_avg", opt.exp_avg)):
+        out[name] = (buf if idx is None else buf.index_select(0, idx)).detach().to(torch.float32).clone()
+    return out
+
+
+def write_outputs(snap, path):
+    """DIR/<name>.npy, float32 (at most 2 x DUMP_SAMPLE elements + the scalars: 32 MiB)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in snap.items():
+        np.save(os.path.join(path, name.replace("/", "_") + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -300,9 +332,15 @@ def main():
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--vocab", type=int, default=600)
     ap.add_argument("--rel-pos", default="latest", choices=["latest", "legacy"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the GEMM / attention rooflines "
+                         "(HIP events on an eager replay of the step), the data-feed rate and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (its stats, and the parameters and Adam first "
+                         "moment it left: snapshot_outputs) as DIR/<name>.npy, float32 (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--feed-steps", type=int, default=5,
-                    help="steps of the data-feed rate (per-step collate + side-stream H2D; 0: skip)")
+                    help="--full: steps of the data-feed rate (per-step collate + side-stream H2D; 0: skip)")
     ap.add_argument("--eager", action="store_true", help="launch kernel by kernel instead of replaying a HIP graph")
     ap.add_argument("--variable-lengths", action="store_true",
                     help="speech lengths U[1000,1500] sorted descending (SURVEY 8(d) variable variant): "
@@ -318,6 +356,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     cmd = rank_launch(sys.argv[1:], args.gpus, os.environ)
     if cmd is not None:
         # the N ranks as child processes (this process has not touched the GPU: counting devices
@@ -368,7 +408,7 @@ def main():
         trainer.train_one_step(batches[i % len(batches)])
     torch.cuda.synchronize()
 
-    if args.eager:
+    if args.eager and args.full:
         K.profile_gemm_start()
     if dp:
         dist.barrier()
@@ -382,6 +422,7 @@ def main():
     elapsed = time.perf_counter() - t0
     # the timed steps must have trained: the last step's loss and gradient norm are finite and
     # no optimizer step was skipped (read after the timed region: no host sync inside it)
+    snap = snapshot_outputs(stats, model, opt) if args.dump_outputs and rank == 0 else None
     last_loss, last_gn = float(stats["loss"].item()), float(stats["grad_norm"].item())
     trainer.resolve_pending()
     trainer.sync_host_state()
@@ -389,12 +430,14 @@ def main():
         print(json.dumps({"error": "non-finite training step", "loss": last_loss, "grad_norm": last_gn,
                           "skipped_steps": trainer.n_skipped}), flush=True)
         sys.exit(3)
+    if snap is not None:
+        write_outputs(snap, args.dump_outputs)
     feed_value = None
-    if args.feed_steps > 0 and not args.variable_lengths:
+    if args.full and args.feed_steps > 0 and not args.variable_lengths:
         feed_value = data_feed_rate(trainer, host_utterances(args.batch, args.vocab, rank), args.feed_steps, world)
         trainer.resolve_pending()
         trainer.sync_host_state()
-    if not args.eager:
+    if args.full and not args.eager:
         # the graph's kernels cannot be bracketed one by one: time the same GEMM launches (same
         # kernels, shapes and inputs) in one eager step right after the timed region
         eager = Trainer(model, opt, sched, TrainerOptions(grad_clip=5.0, use_amp=args.amp), distributed=dp)
@@ -406,8 +449,10 @@ def main():
         K.profile_gemm_start()
         eager.train_one_step(batch)
         eager.resolve_pending()
-    gemm_flops, gemm_ms, gemm_launches, gemm_shapes = K.profile_gemm_stop(by_shape=True)
-    attn_flops, attn_bytes, attn_ms, attn_launches = K.profile_attn_stop()
+    attn_launches = 0
+    if args.full:
+        gemm_flops, gemm_ms, gemm_launches, gemm_shapes = K.profile_gemm_stop(by_shape=True)
+        attn_flops, attn_bytes, attn_ms, attn_launches = K.profile_attn_stop()
 
     el = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if dp:
@@ -420,10 +465,10 @@ def main():
     hbm_peak_gib = round(float(peak.item()), 1)
 
     if rank == 0:
-        traffic = measured_gemm_traffic(args)
+        traffic = measured_gemm_traffic(args) if args.full else {}
         fwd, train = conformer_flops_per_utt(args.d, args.heads, args.ff, args.layers, 2048, 6, args.vocab)
         value = world * args.batch * args.steps / elapsed
-        achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if args.full and gemm_ms > 0 else 0.0
         # fp32 GEMMs of a split build (esp_f32_gemm_products() == 6) issue six bf16 MFMA products
         # per fp32 product: their ceiling is the bf16 MFMA peak / 6
         from espnet_slurp_amd import _native
@@ -431,7 +476,7 @@ def main():
         peak = BF16_MFMA_PEAK_TFLOPS if args.amp else (
             round(BF16_MFMA_PEAK_TFLOPS / 6, 2) if f32_products == 6 else FP32_MFMA_PEAK_TFLOPS)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args)
         out = {
             "metric": "utterances/sec (fbank80x1500, Conformer-12L CTC+attn)",
@@ -460,7 +505,8 @@ def main():
                                    "ctc 0.3, lsm 0.1, dropout 0.1, SpecAug on"
                                    + (", lengths U[1000,1500]" if args.variable_lengths else ""),
                        "global_batch": world * args.batch, "seq_len": 1500, "parallelism": f"dp{world}"},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak,
+            "full": args.full,
+            "roofline": None if not args.full else {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak,
                          "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
                          "f32_mfma_peak_frac": None if args.amp else round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
                          "traffic": traffic.get("hbm_bytes_per_launch"),

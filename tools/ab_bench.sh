@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for i in $(seq 1 $R); do
   for which in A B; do
     if [ $which = A ]; then E="$A"; else E="$B"; fi
-    out=$(env $E timeout -k 10 200 python bench.py --no-cpu-baseline --steps 15 --warmup 3 $ARGS 2>/dev/null | grep '^{') || exit 1
+    out=$(env $E timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 15 --warmup 3 $ARGS 2>/dev/null | grep '^{') || exit 1
     v=$(echo "$out" | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['avg_launch_us'])")
     echo "$which [$E] $v" | tee -a gpurun_out/ab.log
   done
