@@ -71,6 +71,10 @@ SIGNATURES = {
     "esp_glu_bwd_planes": [P, P, P, L, I, L, I, P],
     "esp_dwconv1d": [P, P, P, P, I, I, I, I, I, P, P],
     "esp_dwconv1d_wgrad": [P, P, P, I, I, I, I, P, L, P, P],
+    "esp_csgu_stats": [P, L, I, F, P, P, P],
+    "esp_csgu_fwd": [P, P, P, P, P, P, P, P, I, I, I, I, F, U64, P, P],
+    "esp_csgu_bwd_gate": [P, P, P, P, P, P, P, P, P, L, I, P, P, I, I, I, I, F, U64, P, P],
+    "esp_csgu_bwd_norm": [P, P, P, P, P, P, L, I, P, I, I, I, P, P],
     "esp_bn_swish_fwd": [P, P, P, P, P, P, P, P, F, F, I, I, P, L, I, P, P],
     "esp_bn_swish_eval": [P, P, P, P, P, P, F, I, I, P, P, P],
     "esp_bn_swish_fwd_planes": [P, P, P, P, L, L, I, P, P, P, P, F, F, I, I, P, L, I, P, P],
@@ -132,7 +136,7 @@ _RESTYPES = {"esp_last_error": ctypes.c_char_p, "esp_abi_version": I, "esp_attn_
              "esp_get_gemm_compute": I, "esp_set_splitk_mode": I,
              "esp_f32_gemm_products": I}
 _RESTYPES.update({k: L for k in SIGNATURES if k.endswith("_workspace_bytes")})
-ABI_VERSION = 32  # bumped whenever a signature in include/espnet_mi355.h changes
+ABI_VERSION = 33  # bumped whenever a signature in include/espnet_mi355.h changes
 
 _lib = None
 

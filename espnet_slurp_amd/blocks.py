@@ -193,9 +193,13 @@ class RelPositionMultiHeadedAttention(nn.Module):
         b = f.fused([self.linear_q.bias, self.linear_k.bias, self.linear_v.bias], (3 * D,), grad)
         return w, b
 
-    def fwd(self, x2d, resid, pos_emb, klen, B, T, p_res, seeds: Seeds, training: bool, tvalid=None):
+    def fwd(self, x2d, resid, pos_emb, klen, B, T, p_res, seeds: Seeds, training: bool, tvalid=None, out=None,
+            out_off=0, ldo=None):
         """tvalid (legacy only): the length-bucket T' (ConformerEncoder.run_forward); the legacy
-        rel_shift is taken at T' inside esp_relpos_attn_probs / esp_attn_softmax_bwd_relpos."""
+        rel_shift is taken at T' inside esp_relpos_attn_probs / esp_attn_softmax_bwd_relpos.
+        resid None: drop(linear_out(.)) alone, no residual (the Branchformer's attention branch); out / out_off /
+        ldo: the output is written into columns out_off .. out_off + D of a wider row-major buffer of pitch ldo
+        (the left half of the Branchformer's merge buffer) instead of a new (M, D) tensor."""
         H, dk = self.h, self.d_k
         D = H * dk
         M = B * T
@@ -221,10 +225,11 @@ class RelPositionMultiHeadedAttention(nn.Module):
             stats = empty(Z * T * 2, like=x2d)
             K.relpos_flash_fwd(q_u, q_v, qkv, 3 * D, qkv, 3 * D, p, D, relpos, B, H, math.sqrt(dk), klen, ctx_, D,
                                stats, pa, sa, T, k_off=D, v_off=2 * D)
-            out = empty(M, D, like=x2d)
+            if out is None:
+                out = empty(M, D, like=x2d)
             pr = p_res if training else 0.0
             so = seeds.next()
-            self.linear_out.fwd(ctx_, out, drop_p=pr, seed=so, R=resid, beta=1.0)
+            self.linear_out.fwd(ctx_, out, drop_p=pr, seed=so, R=resid, beta=1.0, out_off=out_off, ldo=ldo)
             return out, Ctx(x=x2d, qkv=qkv, p=p, pos=pos_emb, q_u=q_u, q_v=q_v, ctx=ctx_, stats=stats, klen=klen,
                             flash=True, pa=pa, sa=sa, pr=pr, so=so, B=B, T=T, P=P)
         Tp, Pp = K.pitch(T), K.pitch(P)  # 16-B aligned score rows
@@ -256,10 +261,11 @@ class RelPositionMultiHeadedAttention(nn.Module):
         ctx_ = K.Planes(M, D, x2d.device, npl) if npl else empty(M, D, like=x2d)
         K.gemm(T, dk, T, pv, qkv, ctx_, mode_a=K.KC, lda=Tp, mode_b=K.RC, ldb=3 * D, ldc=D, b_off=2 * D,
                batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(dk, T * 3 * D), sc=(dk, T * D))
-        out = empty(M, D, like=x2d)
+        if out is None:
+            out = empty(M, D, like=x2d)
         pr = p_res if training else 0.0
         so = seeds.next()
-        self.linear_out.fwd(ctx_, out, drop_p=pr, seed=so, R=resid, beta=1.0)
+        self.linear_out.fwd(ctx_, out, drop_p=pr, seed=so, R=resid, beta=1.0, out_off=out_off, ldo=ldo)
         return out, Ctx(x=x2d, qkv=qkv, p=p, pos=pos_emb, q_u=q_u, q_v=q_v, attn=attn, pv=pv, ctx=ctx_,
                         flash=False, pa=pa, sa=sa, pr=pr, so=so, B=B, T=T, P=P, tvalid=tv)
 
@@ -554,6 +560,94 @@ class ConvolutionModule(nn.Module):
         dx = empty(M, D, like=dout)
         K.linear_bwd_data(du, w1.view(2 * D, D), dx)
         return dx
+
+
+CSGU_KMAX = 63  # the depthwise kernels' tap limit (esp_csgu_fwd, esp_dwconv1d)
+
+
+class ConvolutionalSpatialGatingUnit(nn.Module):
+    """espnet2/asr/layers/cgmlp.py:15-81 (gate_activation identity, no linear after the convolution):
+    out = drop(x_r * (dwconv_k(LayerNorm(x_g)) + bias)), x = GELU(v) applied inside the kernels (cgmlp.hip).
+    No mask: the convolution reads an utterance's padded frames like any other frame."""
+
+    def __init__(self, size: int, kernel_size: int, dropout_rate: float, use_linear_after_conv: bool = False,
+                 gate_activation: str = "identity"):
+        super().__init__()
+        if use_linear_after_conv or gate_activation != "identity":
+            raise NotImplementedError("espnet_slurp_amd ConvolutionalSpatialGatingUnit: unsupported "
+                                      f"use_linear_after_conv={use_linear_after_conv}, gate_activation={gate_activation}")
+        if size <= 0 or size % 8:
+            raise ValueError(f"cgmlp_linear_units={size} must be a positive multiple of 8")
+        if kernel_size < 1 or kernel_size % 2 == 0 or kernel_size > CSGU_KMAX:
+            raise ValueError(f"cgmlp_conv_kernel={kernel_size} must be odd and at most {CSGU_KMAX}")
+        n_channels = size // 2
+        self.norm = LayerNorm(n_channels)
+        self.conv = nn.Conv1d(n_channels, n_channels, kernel_size, 1, (kernel_size - 1) // 2, groups=n_channels)
+        self.linear = None
+        self.p = dropout_rate
+        self.kernel_size = kernel_size
+        self.n_channels = n_channels
+
+    def espnet_initialization_fn(self):
+        torch.nn.init.normal_(self.conv.weight, std=1e-6)
+        torch.nn.init.ones_(self.conv.bias)
+
+    def fwd(self, v, B, T, seeds: Seeds, training: bool, tvalid=None):
+        """v (B*T, U): channel_proj1's output before GELU.  Returns (o (B*T, U/2), ctx)."""
+        M = v.shape[0]
+        mean = empty(M, like=v)
+        rstd = empty(M, like=v)
+        K.csgu_stats(v, mean, rstd, self.norm.eps)
+        o = empty(M, self.n_channels, like=v)
+        pd = self.p if training else 0.0
+        sd = seeds.next()
+        K.csgu_fwd(v, mean, rstd, self.norm.weight, self.norm.bias, self.conv.weight, self.conv.bias, o, B, T,
+                   self.kernel_size, drop_p=pd, seed=sd, tvalid=tvalid)
+        return o, Ctx(v=v, mean=mean, rstd=rstd, pd=pd, sd=sd, B=B, T=T, tvalid=tvalid)
+
+    def bwd(self, c, dout):
+        """dout (B*T, U/2) -> dv (B*T, U), Planes when only channel_proj1's gradient GEMMs read it."""
+        M, U = c.v.shape
+        npl = K.planes_mode()
+        dv = K.Planes(M, U, dout.device, npl) if npl else empty(M, U, like=dout)
+        n, cv = self.norm, self.conv
+        K.csgu_bwd(c.v, c.mean, c.rstd, n.weight, n.bias, cv.weight, cv.bias, dout, dv, n.weight.grad, n.bias.grad,
+                   cv.weight.grad, cv.bias.grad, c.B, c.T, self.kernel_size, drop_p=c.pd, seed=c.sd, tvalid=c.tvalid)
+        return dv
+
+
+class ConvolutionalGatingMLP(nn.Module):
+    """cgmlp.py:84-124: channel_proj2(csgu(GELU(channel_proj1(x)))).  channel_proj1 keeps the reference's
+    Sequential(Linear, GELU) key (channel_proj1.0.*); the GELU itself runs inside the csgu kernels."""
+
+    def __init__(self, size: int, linear_units: int, kernel_size: int, dropout_rate: float,
+                 use_linear_after_conv: bool = False, gate_activation: str = "identity"):
+        super().__init__()
+        self.channel_proj1 = nn.Sequential(Linear(size, linear_units), nn.GELU())
+        self.csgu = ConvolutionalSpatialGatingUnit(linear_units, kernel_size, dropout_rate, use_linear_after_conv,
+                                                   gate_activation)
+        self.channel_proj2 = Linear(linear_units // 2, size)
+
+    def fwd(self, x2d, B, T, p_out, seeds: Seeds, training: bool, tvalid=None, out=None, out_off=0, ldo=None):
+        """drop(cgMLP(x2d)) with the block's branch dropout p_out, written into columns out_off .. of `out`
+        (row pitch ldo: the right half of the merge buffer) or a new (M, D) tensor."""
+        p1 = self.channel_proj1[0]
+        v = p1.fwd(x2d)
+        o, c_sg = self.csgu.fwd(v, B, T, seeds, training, tvalid=tvalid)
+        if out is None:
+            out = empty(x2d.shape[0], self.channel_proj2.weight.shape[0], like=o)
+        pr = p_out if training else 0.0
+        so = seeds.next()
+        self.channel_proj2.fwd(o, out, drop_p=pr, seed=so, out_off=out_off, ldo=ldo)
+        return out, Ctx(x=x2d, o=o, sg=c_sg, pr=pr, so=so)
+
+    def bwd(self, c, dout):
+        """dout (M, D) contiguous: gradient of the branch output; returns the gradient of x2d (new buffer)."""
+        dz = grad_buf(dout)
+        K.scale_dropout(dout, dz, drop_p=c.pr, seed=c.so)
+        do = self.channel_proj2.bwd(dz, c.o)
+        dv = self.csgu.bwd(c.sg, do)
+        return self.channel_proj1[0].bwd(dv, c.x)
 
 
 class Conv2dSubsampling(nn.Module):

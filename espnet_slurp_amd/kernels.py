@@ -937,6 +937,56 @@ def dwconv1d_wgrad(dy, x, dW, Bn, T, D, K, tvalid=None):
     _guard_post("esp_dwconv1d_wgrad", ws, n)
 
 
+# ---- the cgMLP's convolutional spatial gating unit (cgmlp.hip): v (B*T, 2C) is channel_proj1's plain output
+def csgu_stats(v, mean, rstd, eps=1e-12):
+    """mean / rstd (M,) of GELU(v[:, C:]) per row."""
+    M, U = v.shape
+    _f32(v, mean, rstd)
+    _native.call("esp_csgu_stats", _p(v), M, U // 2, float(eps), _p(mean), _p(rstd), _st())
+
+
+def csgu_fwd(v, mean, rstd, gamma, beta, W, bias, o, Bn, T, k, drop_p=0.0, seed=0, tvalid=None):
+    """o (B*T, C) = drop(GELU(v_r) * (dwconv_k(LayerNorm(GELU(v_g))) + bias)); dropout keyed as scale_dropout."""
+    C = v.shape[1] // 2
+    _f32(v, mean, rstd, gamma, beta, W, bias, o)
+    assert v.shape[0] == Bn * T and o.shape == (Bn * T, C) and v.is_contiguous() and o.is_contiguous()
+    _native.call("esp_csgu_fwd", _p(v), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(W), _p(bias), _p(o), Bn, T, C, k,
+                 float(drop_p), seed & 0xFFFFFFFFFFFFFFFF, _p(tvalid), _st())
+    return o
+
+
+def csgu_bwd(v, mean, rstd, gamma, beta, W, bias, dout, dv, dgamma, dbeta, dW, dbias, Bn, T, k, drop_p=0.0, seed=0,
+             tvalid=None):
+    """The unit's backward from dout = dL/do (B*T, C): dv (B*T, 2C; fp32 or Planes) is written, the LayerNorm
+    and convolution parameter gradients are accumulated (+=).  Kept from the forward: v and the statistics; g,
+    a and n are recomputed (n written once for the depthwise weight gradient)."""
+    M, U = v.shape
+    C = U // 2
+    _f32(v, mean, rstd, gamma, beta, W, bias, dout)
+    assert M == Bn * T and dout.shape == (M, C) and v.is_contiguous() and dout.is_contiguous()
+    if isinstance(dv, Planes):
+        assert dv.rows == M and dv.cols == U and dv.ld == U
+        pdv, ps, npl = _p(dv.buf), dv.ps, dv.n
+    else:
+        assert dv.shape == (M, U) and dv.is_contiguous()
+        pdv, ps, npl = _p(dv), 0, 0
+    dg = torch.empty_like(dout)
+    n = torch.empty_like(dout)
+    sd = seed & 0xFFFFFFFFFFFFFFFF
+    _native.call("esp_csgu_bwd_gate", _p(v), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(W), _p(bias), _p(dout), pdv,
+                 ps, npl, _p(dg), _p(n), Bn, T, C, k, float(drop_p), sd, _p(tvalid), _st())
+    colsum(dg, dbias, accumulate=True)  # rows beyond tvalid hold 0
+    dwconv1d_wgrad(dg, n, dW, Bn, T, C, k, tvalid=tvalid)
+    dn = torch.empty_like(dout)
+    dwconv1d(dg, W, None, dn, Bn, T, C, k, flip=True, tvalid=tvalid)
+    colsum(dn, dbeta, accumulate=True)
+    pxh = n  # reuse: n is dead after the weight gradient
+    _native.call("esp_csgu_bwd_norm", _p(v), _p(mean), _p(rstd), _p(gamma), _p(dn), pdv, ps, npl, _p(pxh), Bn, T, C,
+                 _p(tvalid), _st())
+    colsum(pxh, dgamma, accumulate=True)
+    return dv
+
+
 def bn_swish_fwd(y, gamma, beta, s, mean, rstd, run_mean, run_var, momentum=0.1, eps=1e-5, T=0, tvalid=None):
     """s: fp32 [M, D] or Planes (esp_bn_swish_fwd_planes)."""
     M, D = y.shape

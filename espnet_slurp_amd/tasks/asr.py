@@ -11,6 +11,7 @@ import torch
 
 from ..asr.ctc import CTC
 from ..asr.decoder.transformer_decoder import TransformerDecoder
+from ..asr.encoder.branchformer_encoder import BranchformerEncoder
 from ..asr.encoder.conformer_encoder import ConformerEncoder
 from ..asr.encoder.transformer_encoder import TransformerEncoder
 from ..asr.espnet_model import ESPnetASRModel
@@ -48,8 +49,8 @@ specaug_choices = ClassChoices("specaug", dict(specaug=SpecAug), default=None, o
 normalize_choices = ClassChoices("normalize", dict(global_mvn=GlobalMVN, utterance_mvn=UtteranceMVN),
                                  default="utterance_mvn", optional=True)
 model_choices = ClassChoices("model", dict(espnet=ESPnetASRModel), default="espnet")
-encoder_choices = ClassChoices("encoder", dict(conformer=ConformerEncoder, transformer=TransformerEncoder),
-                               default="rnn")
+encoder_choices = ClassChoices("encoder", dict(conformer=ConformerEncoder, transformer=TransformerEncoder,
+                                               branchformer=BranchformerEncoder), default="rnn")
 decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder), default="rnn", optional=True)
 
 

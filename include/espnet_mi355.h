@@ -237,6 +237,31 @@ int esp_dwconv1d(const float* x, const float* W, const float* bias, float* y, in
                  int K, int flip, const int* tvalid, void* stream);
 int esp_dwconv1d_wgrad(const float* dy, const float* x, float* dW, int Bn, int T, int D, int K,
                        float* work, long work_bytes, const int* tvalid, void* stream);
+/* ABI 33: the Branchformer cgMLP's convolutional spatial gating unit (cgmlp.py:15-81; gate_activation identity,
+ * no linear after the convolution).  v (B*T, 2C) is channel_proj1's plain output, GELU (erf form) is applied on
+ * load: a_r = GELU(v[:, :C]), a_g = GELU(v[:, C:]), n = LayerNorm_C(a_g) (gamma, beta, eps), g = dwconv_k(n) + bias
+ * over each utterance's own T rows (zero outside [0, T) and at or after *tvalid; no length mask: padded frames
+ * of a short utterance are read like any other), o = drop(a_r * g) with the esp_scale_dropout index r*C + c.
+ * C % 4 == 0, k odd and <= 63, 16-B aligned tensors.  Rows at or after *tvalid are written as 0.
+ *   esp_csgu_stats: mean / rstd (M) of a_g per row.
+ *   esp_csgu_fwd: o (B*T, C); neither a nor n is written.
+ *   esp_csgu_bwd_gate: from dout = dL/do: dv[:, :C] = drop'(dout) g GELU'(v_r), dg = drop'(dout) a_r (B*T, C)
+ *     and n (B*T, C).  dv (B*T, 2C) is fp32 (nplanes 0) or bf16 planes (nplanes 1 / 3, plane p at dv + p * pstride
+ *     bf16 elements, row pitch 2C).
+ *   esp_csgu_bwd_norm: from dn = dL/dn: dv[:, C:] = LN'(dn) GELU'(v_g) and pxh = dn * xhat (B*T, C), whose column
+ *     sum is the LayerNorm weight gradient (dn's is the bias gradient).
+ * Between the two backward calls: dn = esp_dwconv1d(dg, flip), esp_dwconv1d_wgrad(dg, n), esp_colsum(dg). */
+int esp_csgu_stats(const float* v, long M, int C, float eps, float* mean, float* rstd, void* stream);
+int esp_csgu_fwd(const float* v, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                 const float* W, const float* bias, float* o, int B, int T, int C, int k, float drop_p,
+                 unsigned long long seed, const int* tvalid, void* stream);
+int esp_csgu_bwd_gate(const float* v, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                      const float* W, const float* bias, const float* dout, void* dv, long pstride, int nplanes,
+                      float* dg, float* n, int B, int T, int C, int k, float drop_p, unsigned long long seed,
+                      const int* tvalid, void* stream);
+int esp_csgu_bwd_norm(const float* v, const float* mean, const float* rstd, const float* gamma, const float* dn,
+                      void* dv, long pstride, int nplanes, float* pxh, int B, int T, int C, const int* tvalid,
+                      void* stream);
 int esp_bn_swish_fwd(const float* y, const float* gamma, const float* beta, float* s, float* mean,
                      float* rstd, float* run_mean, float* run_var, float momentum, float eps, int M,
                      int D, double* work, long work_bytes, int T, const int* tvalid, void* stream);
