@@ -93,6 +93,7 @@ SIGNATURES = {
     "esp_attn_softmax_bwd_relpos": [P, P, P, P, L, I, F, U64, F, L, I, L, P, P],
     "esp_attn_softmax_bwd_relpos_band": [P, P, P, P, L, F, U64, F, L, I, L, P],
     "esp_relpos_dqv": [P, L, P, L, P, L, I, I, I, P, L, P],
+    "esp_relpos_dq": [P, L, P, L, P, L, P, L, P, I, I, I, P],
     "esp_relpos_attn_bwd": [P, L, P, L, P, P, P, L, I, I, F, F, U64, I, L, P],
     "esp_relpos_flash_fwd": [P, P, P, L, P, L, P, L, I, I, I, F, P, P, L, P, F, U64, I, P],
     "esp_relpos_flash_bwd": [P, P, P, L, P, L, P, L, I, I, I, F, P, P, P, L, P, F, U64, I, P, L, P, P, L, P, P, P],
@@ -136,7 +137,7 @@ _RESTYPES = {"esp_last_error": ctypes.c_char_p, "esp_abi_version": I, "esp_attn_
              "esp_get_gemm_compute": I, "esp_set_splitk_mode": I,
              "esp_f32_gemm_products": I}
 _RESTYPES.update({k: L for k in SIGNATURES if k.endswith("_workspace_bytes")})
-ABI_VERSION = 33  # bumped whenever a signature in include/espnet_mi355.h changes
+ABI_VERSION = 34  # bumped whenever a signature in include/espnet_mi355.h changes
 
 _lib = None
 

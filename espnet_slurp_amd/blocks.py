@@ -255,9 +255,12 @@ class RelPositionMultiHeadedAttention(nn.Module):
             del bd
         attn = ac
         pv = pdrop if pdrop is not None else attn
+        # the dS-only backward (kernels.RELPOS_BWD_DS): latest rel_shift, fp32 compute, no other opt-in form
+        bwd_ds = (not self.legacy and K.RELPOS_BWD_DS and K.relpos_bwd_ds_ok(T, dk) and not K.FUSED_ATTN_BWD
+                  and not K.ATTN_DSCORES and K._COMPUTE[0] == K.GEMM_FP32)
         # ctx feeds only linear_out (forward and weight gradient): planes from the P.V epilogue (the
-        # score-gradient epilogue, ESP_ATTN_DSCORES, reads it in fp32)
-        npl = K.planes_mode() if D % 8 == 0 and not K.ATTN_DSCORES else 0
+        # score-gradient epilogue, ESP_ATTN_DSCORES and the dS-only backward, reads it in fp32)
+        npl = K.planes_mode() if D % 8 == 0 and not K.ATTN_DSCORES and not bwd_ds else 0
         ctx_ = K.Planes(M, D, x2d.device, npl) if npl else empty(M, D, like=x2d)
         K.gemm(T, dk, T, pv, qkv, ctx_, mode_a=K.KC, lda=Tp, mode_b=K.RC, ldb=3 * D, ldc=D, b_off=2 * D,
                batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(dk, T * 3 * D), sc=(dk, T * D))
@@ -267,7 +270,7 @@ class RelPositionMultiHeadedAttention(nn.Module):
         so = seeds.next()
         self.linear_out.fwd(ctx_, out, drop_p=pr, seed=so, R=resid, beta=1.0, out_off=out_off, ldo=ldo)
         return out, Ctx(x=x2d, qkv=qkv, p=p, pos=pos_emb, q_u=q_u, q_v=q_v, attn=attn, pv=pv, ctx=ctx_,
-                        flash=False, pa=pa, sa=sa, pr=pr, so=so, B=B, T=T, P=P, tvalid=tv)
+                        flash=False, pa=pa, sa=sa, pr=pr, so=so, B=B, T=T, P=P, tvalid=tv, bwd_ds=bwd_ds)
 
     def bwd(self, c, dout):
         H, dk = self.h, self.d_k
@@ -281,6 +284,8 @@ class RelPositionMultiHeadedAttention(nn.Module):
         dqkv = empty(M, 3 * D, like=dout)
         if c.flash:
             return self._bwd_flash(c, dctx, dqkv)
+        if c.bwd_ds:
+            return self._bwd_ds(c, dctx, dqkv)
         Tp, Pp = K.pitch(T), K.pitch(P)
         dS = empty(Z * T * Tp, like=dout)
         # the fused dP + softmax/rel_shift adjoint kernel measures slower than the K=64 GEMM + the
@@ -343,6 +348,45 @@ class RelPositionMultiHeadedAttention(nn.Module):
         K.linear_bwd_data(dqkv, w, dx)
         return dx
 
+
+    def _bwd_ds(self, c, dctx, dqkv):
+        """Latest rel_shift backward that reads dS directly (kernels.RELPOS_BWD_DS): the rel_shift adjoint dbd is
+        dS re-indexed, so neither dP nor dbd nor a separate dq_v is formed.  prep (row dots) -> dS from the dP
+        GEMM's epilogue -> dV -> dq = dS k + Dbd p and the pos_bias partials in one kernel -> dk -> dp along
+        dS's diagonals (+ the pos_bias reduction) -> linear_pos weight gradient."""
+        H, dk = self.h, self.d_k
+        D = H * dk
+        B, T, P = c.B, c.T, c.P
+        M, Z = B * T, H * B
+        Tp = K.pitch(T)
+        dS = empty(Z * T * Tp, like=dctx)
+        # dS = P (drop'(dP) - dot) / sqrt(dk), dot_i = dctx_i . ctx_i (= sum_j P_drop dP)
+        dot = empty(Z * T, like=dctx)
+        K.attn_bwd_prep(dctx, D, c.ctx, D, B, H, dk, T, dot, None, 0, 1)
+        K.attn_dscores(dctx, D, c.qkv, 3 * D, c.attn, dot, dS, None, 0, 1, B, H, dk, math.sqrt(dk), c.pa, c.sa, T,
+                       Tp, v_off=2 * D)
+        # dV = pv^T dctx -> dqkv[:, 2D:3D]
+        K.gemm(T, dk, T, c.pv, dctx, dqkv, mode_a=K.RC, lda=Tp, mode_b=K.RC, ldb=D, ldc=3 * D, c_off=2 * D,
+               batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(dk, T * D), sc=(dk, T * 3 * D))
+        # dq = dq_u + dq_v -> dqkv[:, 0:D]; per-block column sums of each for the pos_bias gradients
+        bias_part = empty(Z * ((T + 31) // 32) * 2 * dk, like=dctx)
+        K.relpos_dq(dS, Tp, c.qkv, 3 * D, c.p, D, dqkv, 3 * D, bias_part, B, H, T, k_off=D)
+        # dk = dS^T q_u -> dqkv[:, D:2D]
+        K.gemm(T, dk, T, dS, c.q_u, dqkv, mode_a=K.RC, lda=Tp, mode_b=K.RC, ldb=dk, ldc=3 * D, c_off=D,
+               batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(B * T * dk, T * dk), sc=(dk, T * 3 * D))
+        # dp[:, h] = sum_b Dbd[h,b]^T q_v[h,b]; pos_bias_u / pos_bias_v grads += the partials, in fixed order
+        dp = empty(P, D, like=dctx)
+        K.relpos_dp(dS, Tp, c.q_v, 1, B, H, T, dp, D, bias_part, None, self.pos_bias_u.grad.view(-1),
+                    self.pos_bias_v.grad.view(-1), dqkv, 3 * D)
+        del dS
+        K.gemm(D, D, P, dp, c.pos, self.linear_pos.weight.grad, mode_a=K.RC, lda=D, mode_b=K.RC, ldb=D, ldc=D,
+               R=self.linear_pos.weight.grad, beta=1.0)
+        w, _ = self._wqkv()
+        gw, gb = self._wqkv(grad=True)
+        K.linear_bwd_weight(dqkv, c.x, gw, gb)
+        dx = empty(M, D, like=dctx)
+        K.linear_bwd_data(dqkv, w, dx)
+        return dx
 
     def _bwd_flash(self, c, dctx, dqkv):
         """Flash backward: scores recomputed per (z, 32 rows); dq (q_u and q_v paths) and the

@@ -59,7 +59,7 @@ __global__ void heads_split2_kernel(const float* __restrict__ src, long ld, int 
 // Attention backward prep (esp_attn_bwd_prep), one wave per score row (z, i), z = h*nb + b:
 //   dot[z*T + i] = dctx[b*T+i][h*dk ..] . ctx[b*T+i][h*dk ..]  (= sum_j P_drop[i][j] dP[i][j])
 //   and the bd-gradient elements the score-gradient epilogue never writes set to 0:
-//   latest: k < T-1-i and k >= 2T-1-i;  legacy: row 0's k < T-1.
+//   latest: k < T-1-i and k >= 2T-1-i;  legacy: row 0's k < T-1.  (dbd NULL: the dots only.)
 __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const float* __restrict__ dctx, long ldd,
                                                             const float* __restrict__ ctx, long ldc, int nb, int H,
                                                             int dk, int T, float* __restrict__ dot,
@@ -75,6 +75,7 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const float* __restr
   for (int d = lane; d < dk; d += 64) acc += dctx[src * ldd + h * dk + d] * ctx[src * ldc + h * dk + d];
   acc = esp::wave_sum(acc);
   if (lane == 0) dot[row] = acc;
+  if (!dbd) return;  // the dS-only backward: the row dots alone
   float* br = dbd + row * ldp;
   const int sh = T - 1 - i;
   if (relpos == 1) {
@@ -1653,12 +1654,39 @@ ESP_API int esp_heads_split2(const float* src, long ld, int col0, int B, int T, 
   return 0;
 }
 
+// the dots alone for d_k = 64 (the dS-only backward): 16 lanes per row, one float4 of each operand per lane
+static __global__ __launch_bounds__(256) void attn_bwd_dots64_kernel(const float* __restrict__ dctx, long ldd,
+                                                              const float* __restrict__ ctx, long ldc, int nb, int T,
+                                                              long rows, float* __restrict__ dot) {
+  const long row = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const int part = threadIdx.x & 15;
+  const long rc = row < rows ? row : rows - 1;
+  const int i = (int)(rc % T);
+  const int z = (int)(rc / T);
+  const int h = z / nb, b = z - h * nb;
+  const long src = (long)b * T + i;
+  const float4 g = *reinterpret_cast<const float4*>(dctx + src * ldd + h * 64 + 4 * part);
+  const float4 c = *reinterpret_cast<const float4*>(ctx + src * ldc + h * 64 + 4 * part);
+  float s = g.x * c.x + g.y * c.y + g.z * c.z + g.w * c.w;
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  s += __shfl_xor(s, 4, 64);
+  s += __shfl_xor(s, 8, 64);
+  if (part == 0 && row < rows) dot[row] = s;
+}
+
 ESP_API int esp_attn_bwd_prep(const float* dctx, long ldd, const float* ctx, long ldc, int nb, int H, int dk, int T,
                               float* dot, float* dbd, long ldp, int relpos, void* stream) {
   ESP_ARG_CHECK(relpos == 1 || relpos == 2, "esp_attn_bwd_prep: relpos must be 1 or 2");
-  ESP_ARG_CHECK(T >= 1 && nb >= 1 && H >= 1 && dk >= 1 && ldp >= (relpos == 1 ? 2 * T - 1 : T),
+  ESP_ARG_CHECK(T >= 1 && nb >= 1 && H >= 1 && dk >= 1 && (!dbd || ldp >= (relpos == 1 ? 2 * T - 1 : T)),
                 "esp_attn_bwd_prep: bad sizes");
   const long rows = (long)nb * H * T;
+  if (!dbd && dk == 64 && ldd % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)dctx & 15) == 0 && ((uintptr_t)ctx & 15) == 0) {
+    hipLaunchKernelGGL(attn_bwd_dots64_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, (hipStream_t)stream,
+                       dctx, ldd, ctx, ldc, nb, T, rows, dot);
+    ESP_CHECK_LAUNCH("esp_attn_bwd_prep");
+    return 0;
+  }
   hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dctx,
                      ldd, ctx, ldc, nb, H, dk, T, dot, dbd, ldp, relpos);
   ESP_CHECK_LAUNCH("esp_attn_bwd_prep");

@@ -539,7 +539,7 @@ __global__ __launch_bounds__(BW_NT, 1) void relpos_flash_bwd_kernel(FlashArgs a)
 template <int REL>
 __global__ __launch_bounds__(256) void relpos_dp_kernel(const float* __restrict__ dS, long lds,
                                                         const float* __restrict__ qv, int nb, int T, int bpg,
-                                                        float* __restrict__ dp_part) {
+                                                        float* __restrict__ dp_part, long qv_rows) {
   __shared__ float part[2][FR][FDK + 4];
   const int P2 = 2 * T - 1;
   const int nxt = (P2 + 31) / 32;
@@ -547,7 +547,7 @@ __global__ __launch_bounds__(256) void relpos_dp_kernel(const float* __restrict_
   const int rest = blockIdx.x / ((nb + bpg - 1) / bpg);
   const int xt = rest % nxt, h = rest / nxt;
   const int ng = (nb + bpg - 1) / bpg;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (wave-uniform)
   const int hf = lane >> 5, l32 = lane & 31;
   const int c = wave & 1, half = wave >> 1;
   const int x = xt * 32 + l32;  // this lane's position row (A row)
@@ -556,10 +556,48 @@ __global__ __launch_bounds__(256) void relpos_dp_kernel(const float* __restrict_
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   const int nrc = (T + 31) / 32;  // rho chunks of 32 (K dimension per batch element)
   const int b0 = g * bpg, nbb = min(nb, (g + 1) * bpg) - b0;
-  const int nit = nbb * ((nrc - half + 1) / 2);  // (batch, this half's rho chunks) iterations
+  // latest: position tile xt meets dS only in the rho chunks with a key j = x - (T-1) + rho in [0, T) for some
+  // x of the tile; the other (tile, chunk) pairs, about half, are all zeros and are skipped
+  const int x0 = xt * 32;
+  const int rc_lo = REL == 1 ? max(0, (T - 1 - x0 - 62 + 31) / 32) : 0;  // (a negative numerator truncates to 0)
+  const int rc_hi = REL == 1 ? min(nrc, (2 * T - 1 - x0 + 31) / 32) : nrc;
+  const int per = max(0, (rc_hi - rc_lo - half + 1) / 2);  // this half's chunks: rc_lo + half, + 2, ..
+  const int nit = nbb * per;                                // (batch, chunk) iterations
+  // latest: the iterations come in order, so (utterance, chunk) are counters, and both operands come through
+  // buffer loads whose per-element address is one add: element s of the lane is row rho0 + 16 hf + s, key
+  // jj = (x0 - (T-1) + rho0) + l32 + 16 hf + s of the utterance's dS matrix (the buffer: a row >= T is out of
+  // range and reads 0; a key outside [0, T) would be the neighbouring row's and is zeroed by predicate), and
+  // q_v row rho0 + 16 hf + s (an immediate offset; past the tensor's end the buffer reads 0)
+  int nx_b = 0, nx_k = 0;
+  const uint32_t a_lane = (uint32_t)((16 * hf) * (lds + 1) + l32) * 4u, a_step = (uint32_t)(lds + 1) * 4u;
+  const uint32_t b_lane = (uint32_t)(16 * hf * FDK + l32) * 4u;
   auto load_it = [&](int it, float (&af)[16], float (&bf)[16]) {
-    const int per = (nrc - half + 1) / 2;
-    const int bb = b0 + it / per, rc = half + 2 * (it % per);
+    if constexpr (REL == 1) {
+      const long zrow = (long)(h * nb + b0 + nx_b) * T;
+      const int rho0 = (rc_lo + half + 2 * nx_k) * 32;
+      if (++nx_k == per) {
+        nx_k = 0;
+        ++nx_b;
+      }
+      const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float*>(dS + zrow * lds), (short)0, (int)((long)T * lds * 4), 0x00020000);
+      const long brem = (qv_rows - (zrow + rho0)) * FDK * 4 - 32 * c * 4;
+      const __amdgpu_buffer_rsrc_t br = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float*>(qv + (zrow + rho0) * FDK + 32 * c), (short)0, (int)(brem < 0x7fffffffL ? brem : 0x7fffffffL),
+          0x00020000);
+      const int uj = x0 - (T - 1) + rho0;
+      const uint32_t a_it = (uint32_t)(rho0 * (int)lds + uj) * 4u;  // (negative: wraps past the buffer -> 0)
+      const int jl = uj + l32 + 16 * hf;
+#pragma unroll
+      for (int s = 0; s < 16; ++s) {
+        const float v = __builtin_bit_cast(
+            float, __builtin_amdgcn_raw_buffer_load_b32(ar, (int)(a_lane + (a_it + (uint32_t)s * a_step)), 0, 0));
+        af[s] = (uint32_t)(jl + s) < (uint32_t)T ? v : 0.f;
+        bf[s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(br, (int)b_lane + s * FDK * 4, 0, 0));
+      }
+      return;
+    }
+    const int bb = b0 + it / per, rc = rc_lo + half + 2 * (it % per);
     const long zrow = (long)(h * nb + bb) * T;
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
@@ -779,8 +817,10 @@ ESP_API int esp_relpos_dp(const float* dS, long lds, const float* qv, int rel, i
   hipStream_t st = (hipStream_t)stream;
   const int nxt = (P2 + 31) / 32;
   const dim3 grid((unsigned)(H * nxt * ng));
-  if (rel == 1) hipLaunchKernelGGL(relpos_dp_kernel<1>, grid, dim3(256), 0, st, dS, lds, qv, nb, T, bpg, work);
-  else hipLaunchKernelGGL(relpos_dp_kernel<2>, grid, dim3(256), 0, st, dS, lds, qv, nb, T, bpg, work);
+  const long qv_rows = (long)nb * H * T;
+  ESP_ARG_CHECK((long)T * lds * 4 < (1L << 31), "esp_relpos_dp: T * lds too large for 32-bit row offsets");
+  if (rel == 1) hipLaunchKernelGGL(relpos_dp_kernel<1>, grid, dim3(256), 0, st, dS, lds, qv, nb, T, bpg, work, qv_rows);
+  else hipLaunchKernelGGL(relpos_dp_kernel<2>, grid, dim3(256), 0, st, dS, lds, qv, nb, T, bpg, work, qv_rows);
   const int P = rel == 2 ? T : P2;
   long nb_red = ((long)H * P * FDK + 255) / 256;
   if (nb_red > 8192) nb_red = 8192;

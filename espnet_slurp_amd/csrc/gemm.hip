@@ -171,7 +171,7 @@ bool launch_glds(int MA, int MB, const GemmArgs& g, int batch, hipStream_t st, c
     if ((kind == EPI_FFN_SWISH_PL || kind == EPI_FFN_RELU_PL) && !(MA == KC && MB == KC)) return false;
     if ((kind == EPI_BMUL_PL || kind == EPI_RMASK_PL) && !(MA == KC && MB == RC)) return false;
   }
-  if (kind == EPI_SMB && !(MA == KC && MB == KC && g.bf16 == 0)) return false;
+  if ((kind == EPI_SMB || kind == EPI_SMBN) && !(MA == KC && MB == KC && g.bf16 == 0)) return false;
   if (!g.cpn && (((kind == EPI_BMUL || kind == EPI_RMASK) && !can_spec_bwd) || ((kind == EPI_P0 || kind == EPI_PR) && !can_pspec) ||
       (kind == EPI_RMASKMAP && !(MA == I2CT_KC && MB == RC)) ||
       (kind == EPI_BRELU && !can_brelu) ||
@@ -207,7 +207,7 @@ bool launch_glds(int MA, int MB, const GemmArgs& g, int batch, hipStream_t st, c
   const int prec = g.bf16;
   if (kind == EPI_PLAIN) return glds_launch_plain(MA, MB, BNT, prec, rs, grid, st, g, x);
   if (kind == EPI_FWD || kind == EPI_BWD) return glds_launch_epi(MA, MB, BNT, prec, kind, grid, st, g, x);
-  if (kind == EPI_P0 || kind == EPI_PR || kind == EPI_SMB || kind == EPI_P0_PL)
+  if (kind == EPI_P0 || kind == EPI_PR || kind == EPI_SMB || kind == EPI_SMBN || kind == EPI_P0_PL)
     return glds_launch_pspec(MA, MB, BNT, prec, kind, grid, st, g, x);
   return glds_launch_spec(MA, MB, BNT, prec, kind, grid, st, g, x);
 }
@@ -481,12 +481,13 @@ ESP_API int esp_gemm_bf16_pl(int mode_a, int mode_b, int M, int N, int K, int ba
 // into the bd gradient rows (latest / legacy rel_shift adjoint; esp_attn_bwd_prep zeroes the
 // elements without a source).  Replaces the dP GEMM + the row-wise softmax / rel_shift pass
 // (attention.py:64-96, 145-165 backward): no dP tensor round trip through HBM.
+// dbd NULL: dS alone (EPI_SMBN), for the backward whose dq / dp kernels read dS along its diagonals.
 ESP_API int esp_attn_dscores(const float* dctx, long ldd, const float* vmat, long ldv, const float* attn,
                              const float* dot, float* dS, float* dbd, long ldp, int relpos, int nb, int H, int dk,
                              float sqrt_dk, float drop_p, unsigned long long seed, int T, long lds, void* stream) {
   ESP_ARG_CHECK(relpos == 1 || relpos == 2, "esp_attn_dscores: relpos must be 1 or 2");
   ESP_ARG_CHECK(T >= 1 && nb >= 1 && H >= 1 && dk >= 1 && lds >= T && lds % 4 == 0 &&
-                    ldp >= (relpos == 1 ? 2 * T - 1 : T) && sqrt_dk > 0.f,
+                    (!dbd || ldp >= (relpos == 1 ? 2 * T - 1 : T)) && sqrt_dk > 0.f,
                 "esp_attn_dscores: bad sizes T=%d lds=%ld ldp=%ld", T, lds, ldp);
   ESP_ARG_CHECK(((uintptr_t)attn & 15) == 0 && ((uintptr_t)dS & 15) == 0, "esp_attn_dscores: attn / dS not 16-B aligned");
   GemmArgs smb{};

@@ -1,6 +1,7 @@
 // Instantiations of gemm_glds_kernel with the specialised plain epilogues (EPI_P0: alpha*acc,
 // EPI_PR: alpha*acc + beta*R; unsplit, wide stores) for the linear / attention mode pairs, and the
-// attention score-gradient epilogue (EPI_SMB, KC x KC fp32: esp_attn_dscores).
+// attention score-gradient epilogues (EPI_SMB, and EPI_SMBN without the dbd scatter; KC x KC fp32:
+// esp_attn_dscores).
 // See store_spec in gemm_kernels.h.
 #include "gemm_kernels.h"
 
@@ -27,6 +28,9 @@ bool glds_launch_pspec(int ma, int mb, int bnt, int prec, int epi, dim3 grid, hi
       } else if constexpr (MA == KC && MB == KC && BF == 0) {
         if (epi == EPI_SMB) {
           hipLaunchKernelGGL((gemm_glds_kernel<MA, MB, BNT, false, EPI_SMB, BF, BMT>), grid, dim3(glds_threads(BMT)), 0, st, g, x);
+          ok = true;
+        } else if (epi == EPI_SMBN) {
+          hipLaunchKernelGGL((gemm_glds_kernel<MA, MB, BNT, false, EPI_SMBN, BF, BMT>), grid, dim3(glds_threads(BMT)), 0, st, g, x);
           ok = true;
         }
       }

@@ -189,7 +189,9 @@ enum { EPI_PLAIN = 0, EPI_FWD = 1, EPI_BWD = 2, EPI_BIAS = 3, EPI_BDR = 4, EPI_F
        // ... and the gradient through a ReLU output (the subsampling's dz2: its readers are conv2's GEMMs)
        EPI_RMASK_PL = 18,
        // EPI_RMASKMAP (bit-map mask) that writes no C: the conv1 weight gradient folded in (store_c1fold)
-       EPI_C1FOLD = 19 };
+       EPI_C1FOLD = 19,
+       // EPI_SMB without the rel_shift adjoint (smb_dbd NULL): dS alone, for the backward that reads dS directly
+       EPI_SMBN = 20 };
 // the fp32-output kind a planes-output kind computes
 constexpr int epi_base(int e) {
   return e == EPI_FFN_SWISH_PL ? EPI_FFN_SWISH
@@ -205,7 +207,7 @@ __host__ __device__ inline int epi_kind(const GemmArgs& g) {
 // the specialised kind (store_spec) when the launch's features match one exactly, else the
 // generic kind; only for wide (float4) epilogues (the conv2 output row map: EPI_RMASKMAP only)
 __host__ inline int epi_kind_spec(const GemmArgs& g) {
-  if (g.smb_rel) return EPI_SMB;
+  if (g.smb_rel) return g.smb_dbd ? EPI_SMB : EPI_SMBN;
   const int k = epi_kind(g);
   if (g.cpn) {  // planes output: the kinds that have a planes form, else none (-1)
     if (g.splits > 1 || g.rowsum || g.r) return -1;
@@ -478,6 +480,7 @@ __device__ __forceinline__ void store_tiles_wide(const GemmArgs& g, int z, int m
 //   EPI_PR         alpha * acc + beta * R                        (gradient accumulation)
 //   EPI_SMB        dS = P * (drop'(acc) - dot_row) * alpha -> C, and its rel_shift adjoint -> dbd
 //                  (attention.py:64-96 + 145-165 backward; P in pre, FlashAttention-2's row dot)
+//   EPI_SMBN       EPI_SMB's dS alone: one P quad load and one dS quad store per lane and row, no dbd
 // (wide stores, no output row map but EPI_RMASKMAP's; chosen by epi_kind on the host).  A wave whose 32-row /
 // 32-column sub-tiles are all in range takes a path without per-element bounds checks.
 template <int EPI_>
@@ -510,26 +513,46 @@ __device__ __forceinline__ void store_spec(const GemmArgs& g, int z, int mrow0, 
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       quad_transpose(acc[i][j], lane);
-      if constexpr (EPI == EPI_SMB) {
+      if constexpr (EPI == EPI_SMB || EPI == EPI_SMBN) {
         // lane: rows m (q = 0..3) x columns n..n+3; M = N = T (one (head, utterance) per z)
         const int T = g.M;
         const uint64_t kseed = esp::keyed(g.seed, g.key);
+        // the whole mask index range below 2^32: the 32-bit hash forms draw the same masks
+        const bool idx32 = (uint64_t)g.batch * (uint64_t)g.M * (uint64_t)g.N < (1ull << 32);
+        // the four rows' P quads and row dots are requested before the first store: C may alias nothing the
+        // compiler can prove, so a load placed after a store would wait for it (one round trip per row)
+        float4 pq[4];
+        float dq4[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int m = mrow0 + i * 32 + 8 * q + 4 * h + (l32 & 3);
+          const bool ok = nok && m < g.M;
+          pq[q] = ok ? *reinterpret_cast<const float4*>(g.pre + cbase + (long)m * g.ldc + n) : zero4;  // rows padded to whole quads
+          dq4[q] = ok ? g.smb_dot[(long)z * T + m] : 0.f;
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int m = mrow0 + i * 32 + 8 * q + 4 * h + (l32 & 3);
           if (!nok || m >= g.M) continue;
           const long off = cbase + (long)m * g.ldc + n;
-          const float4 pa = *reinterpret_cast<const float4*>(g.pre + off);  // rows padded to whole quads
-          const float pr[4] = {pa.x, pa.y, pa.z, pa.w};
+          const float pr[4] = {pq[q].x, pq[q].y, pq[q].z, pq[q].w};
           const long zr = (long)z * T + m;
-          const float dot = g.smb_dot[zr];
+          const float dot = dq4[q];
           const uint64_t row = dbase + (uint64_t)m * (uint64_t)g.N + n;
-          float* db = g.smb_dbd + zr * g.smb_ldp;
           float v[4];
+          bool kp[4] = {true, true, true, true};
+          if (g.drop_thresh) {
+            if (idx32 && !(row & 1)) {  // an even first index (every row when T is even): one hash per pair
+              esp::keep_pair32(kseed, (uint32_t)row, g.drop_thresh, kp[0], kp[1]);
+              esp::keep_pair32(kseed, (uint32_t)row + 2, g.drop_thresh, kp[2], kp[3]);
+            } else {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) kp[e] = esp::keep_elem(kseed, row + e, g.drop_thresh);
+            }
+          }
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            float gv = acc[i][j][4 * q + e];
-            if (g.drop_thresh) gv = esp::keep_elem(kseed, row + e, g.drop_thresh) ? gv * g.drop_scale : 0.f;
+            const float gv = kp[e] ? acc[i][j][4 * q + e] * g.drop_scale : 0.f;
             v[e] = pr[e] * (gv - dot) * g.alpha;
           }
           if (n + 4 <= g.N) {
@@ -539,12 +562,15 @@ __device__ __forceinline__ void store_spec(const GemmArgs& g, int z, int mrow0, 
             for (int e = 0; e < 4; ++e)
               if (n + e < g.N) g.c[off + e] = v[e];
           }
+          if constexpr (EPI == EPI_SMB) {
+            float* db = g.smb_dbd + zr * g.smb_ldp;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int jj = n + e;
-            if (jj >= g.N) continue;
-            if (g.smb_rel == 1 || jj <= m) db[jj + T - 1 - m] = v[e];
-            else if (jj >= m + 2) db[g.smb_ldp + jj - m - 2] = v[e];  // legacy: row m+1's lower part
+            for (int e = 0; e < 4; ++e) {
+              const int jj = n + e;
+              if (jj >= g.N) continue;
+              if (g.smb_rel == 1 || jj <= m) db[jj + T - 1 - m] = v[e];
+              else if (jj >= m + 2) db[g.smb_ldp + jj - m - 2] = v[e];  // legacy: row m+1's lower part
+            }
           }
         }
         continue;
@@ -753,7 +779,7 @@ template <int EPI, int TM, int TN>
 __device__ __forceinline__ void store_spec_tiles(const GemmArgs& g, int z, int mrow0, int ncol0, int lane,
                                                  f32x16 (&acc)[TM][TN]) {
   const bool full = mrow0 + TM * 32 <= g.M && ncol0 + TN * 32 <= g.N;
-  if (EPI != EPI_SMB && g.alpha == 1.0f) {
+  if (EPI != EPI_SMB && EPI != EPI_SMBN && g.alpha == 1.0f) {
     if (full) store_spec<EPI, TM, TN, true, true>(g, z, mrow0, ncol0, lane, acc);
     else store_spec<EPI, TM, TN, false, true>(g, z, mrow0, ncol0, lane, acc);
   } else {

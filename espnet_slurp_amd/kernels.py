@@ -1087,7 +1087,8 @@ def relpos_attn_probs(q_u, q_v, kmat, ldk, p, ldp_row, relpos, nb, H, sqrt_dk, k
 
 
 def attn_bwd_prep(dctx, ldd, ctx, ldc, nb, H, dk, T, dot, dbd, ldp, relpos):
-    """Row dots dctx_i . ctx_i per head and the source-less bd-gradient elements zeroed."""
+    """Row dots dctx_i . ctx_i per head and the source-less bd-gradient elements zeroed (dbd None: the dots
+    alone)."""
     _f32(dctx, ctx, dot, dbd)
     _native.call("esp_attn_bwd_prep", _p(dctx), ldd, _p(ctx), ldc, nb, H, dk, T, _p(dot), _p(dbd), ldp, int(relpos),
                  _st())
@@ -1095,7 +1096,7 @@ def attn_bwd_prep(dctx, ldd, ctx, ldc, nb, H, dk, T, dot, dbd, ldp, relpos):
 
 def attn_dscores(dctx, ldd, vmat, ldv, attn, dot, dS, dbd, ldp, relpos, nb, H, dk, sqrt_dk, drop_p, seed, T, lds,
                  v_off=0):
-    """dS and the rel_shift-adjoint dbd straight from the dP = dctx V^T GEMM's epilogue."""
+    """dS and the rel_shift-adjoint dbd straight from the dP = dctx V^T GEMM's epilogue (dbd None: dS alone)."""
     _f32(dctx, vmat, attn, dot, dS, dbd)
     if _PROF is not None:
         ev0 = torch.cuda.Event(enable_timing=True)
@@ -1105,9 +1106,10 @@ def attn_dscores(dctx, ldd, vmat, ldv, attn, dot, dS, dbd, ldp, relpos, nb, H, d
                  int(relpos), nb, H, dk, float(sqrt_dk), float(drop_p), int(seed) & (2 ** 64 - 1), T, lds, _st())
     if _PROF is not None:
         ev1.record()
-        # epilogue streams besides A, B, C: P read, dbd written (band) — M x N per batch each
+        # epilogue streams besides A, B, C: P read, dbd written (band; not in the dS-only form) — M x N per
+        # batch each
         _PROF.append((2.0 * T * T * dk * nb * H, ev0, ev1, (KC, KC, T, T, dk, nb * H, "dscores"),
-                      8.0 * T * T * nb * H))
+                      (8.0 if dbd is not None else 4.0) * T * T * nb * H))
 
 
 def relpos_probs_ok(T: int, dk: int) -> bool:
@@ -1153,6 +1155,34 @@ def relpos_dqv(dbd, ldp, p, ldpm, out, ldo, nb, H, T):
         _PROF.append((2.0 * T * 64 * T * nb * H, ev0, ev1, (KC, RC, T, 64, T, nb * H, "band"), 0.0))
 
 
+# RELPOS_BWD_DS = True (default): the latest rel-pos attention backward reads dS directly -- the score gradient
+# from the dP GEMM's epilogue without the dbd scatter (esp_attn_dscores, dbd None), dq = dS k + Dbd p in one
+# kernel over the staged dS rows (esp_relpos_dq) and dp along dS's diagonals (esp_relpos_dp): no dP, dbd or
+# dq_v tensor.  False: the row-wise adjoint pass + dbd band (A/B measurements, and the tests of that path).
+RELPOS_BWD_DS = True
+
+
+def relpos_bwd_ds_ok(T: int, dk: int) -> bool:
+    """Whether the dS-only backward covers this shape: d_k 64, the 32 staged dS rows in 64 KB of LDS
+    (T <= 480), score pitch % 4 == 0 (always, with SCORE_ALIGN 4)."""
+    return dk == 64 and 1 <= T <= 480 and pitch(T) % 4 == 0
+
+
+def relpos_dq(dS, lds, kmat, ldk, p, ldpm, dq, ldq, bias_part, nb, H, T, k_off=0, dq_off=0):
+    """dq[:, head h] = dS k + Dbd p (dq_u + dq_v) from the staged dS rows, and the per-block pos_bias column
+    sums (esp_relpos_dq; latest, d_k = 64)."""
+    _f32(dS, kmat, p, dq, bias_part)
+    if _PROF is not None:
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    _native.call("esp_relpos_dq", _p(dS), lds, _p(kmat, k_off), ldk, _p(p), ldpm, _p(dq, dq_off), ldq, _p(bias_part),
+                 nb, H, T, _st())
+    if _PROF is not None:  # algorithmic work: dS k and the T band columns per row of Dbd p
+        ev1.record()
+        _PROF.append((4.0 * T * 64 * T * nb * H, ev0, ev1, (KC, RC, T, 64, 2 * T, nb * H, "dq_ds"), 0.0))
+
+
 # dbd buffers of the latest rel_shift adjoint, kept per (device, Z, T, pitch) and zeroed once: the band
 # kernel writes each row's T band columns only, so the rest stays 0 for every layer and step (half the
 # adjoint's dbd bytes).  Made outside graph capture only (a buffer made inside would live in the graph's
@@ -1191,9 +1221,12 @@ FUSED_ATTN_BWD = False
 # the 16-row-wave kernel (esp_relpos_attn_probs); kept for A/B measurements
 ATTN_FWD32 = False
 # ATTN_DSCORES = True: the softmax / rel_shift adjoints in the dP GEMM's epilogue (esp_attn_dscores,
-# FlashAttention-2's row dot) instead of the dP GEMM + the row-wise adjoint pass.  Opt-in: measured
-# at C2 B=128 it is 412 + 73 us per layer against 59 + 266 (the epilogue's rel_shift scatter is one
-# scalar store per element; the row-wise pass writes each shifted bd row contiguously)
+# FlashAttention-2's row dot) WITH the dbd scatter, instead of the dP GEMM + the row-wise adjoint pass, for
+# the paths that still form dbd (legacy, RELPOS_BWD_DS off).  Opt-in: measured at C2 B=128 it is 412 + 73 us
+# per layer against 59 + 266 (the epilogue's rel_shift scatter is one scalar store per element; the row-wise
+# pass writes each shifted bd row contiguously).  The default latest backward (RELPOS_BWD_DS) uses the same
+# epilogue without dbd: 648 us per layer at C2 B=384 against 316 + 657 for the GEMM + row-wise pass it replaces
+#  -- still 3x its memory floor, so the scatter was not the epilogue's whole cost.
 ATTN_DSCORES = False
 def relpos_attn_bwd(dctx, ldd, vmat, ldv, attn, dS, dbd, ldp, nb, H, sqrt_dk, drop_p, seed, T, lds, v_off=0):
     """Fused latest rel-pos attention backward: dP = dctx V^T (MFMA), dropout/softmax/rel_shift adjoints."""

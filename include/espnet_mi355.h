@@ -352,6 +352,15 @@ int esp_relpos_flash_bwd(const float* qu, const float* qv, const float* kmat, lo
 int esp_relpos_dp(const float* dS, long lds, const float* qv, int rel, int nb, int H, int T, float* dp, long ldp,
                   const float* bias_part, const float* carry, float* du, float* dv, float* dq, long ldq,
                   float* work, long work_floats, void* stream);
+/* ABI 34: the query gradient of latest rel-pos attention straight from dS (csrc/attention_bwd.hip; d_k = 64,
+ * T <= 480): dq (rows b*T + i, pitch ldq, head h at column 64 h; overwritten) = dS k + Dbd p, the rel_shift
+ * adjoint Dbd[i][T-1-i+j] = dS[i][j] read from the staged dS rows with a per-row skew (no dbd tensor), on the
+ * GEMMs' six bf16 split products.  dS: nb*H*T rows of pitch lds (% 4 == 0, 16-B aligned), z = h*nb + b; k rows
+ * at kmat + (b*T + j)*ldk + 64 h; p: 2T-1 rows of pitch ldpm, head h at column 64 h.  bias_part
+ * (nb*H, ceil(T/32), 2, 64): per-block column sums of dq_u and dq_v, which esp_relpos_dp reduces in fixed order
+ * into the pos_bias_u / pos_bias_v gradients. */
+int esp_relpos_dq(const float* dS, long lds, const float* kmat, long ldk, const float* p, long ldpm, float* dq,
+                  long ldq, float* bias_part, int nb, int H, int T, void* stream);
 /* Fused latest rel-pos scores + softmax (attention.py:240-263 with the latest rel_shift,
  * embedding.py:173-244): bd_shift[i][j] = q_v[i] . p[j + T-1-i] is computed on the MFMA per
  * 32-row block inside the kernel (no (Z,T,2T-1) bd tensor), then s = (ac + bd_shift)/sqrt(dk),
@@ -378,6 +387,8 @@ int esp_relpos_attn_fwd(const float* qu, const float* qv, const float* kmat, lon
  * ctx (B*T, H*dk) rows of pitch ldd / ldc; V rows at vmat + (b*T + j)*ldv + h*dk; attn / dS
  * (Z,T) rows of pitch lds, 16-B aligned).  Replaces the dP GEMM + esp_attn_softmax_bwd_relpos
  * (attention.py:64-96, 145-165 backward). */
+/* ABI 34: dbd NULL in both: the row dots alone / dS alone (no rel_shift adjoint scatter), for the backward
+ * that reads dS directly (esp_relpos_dq, esp_relpos_dp). */
 int esp_attn_bwd_prep(const float* dctx, long ldd, const float* ctx, long ldc, int nb, int H, int dk, int T,
                       float* dot, float* dbd, long ldp, int relpos, void* stream);
 int esp_attn_dscores(const float* dctx, long ldd, const float* vmat, long ldv, const float* attn, const float* dot,
