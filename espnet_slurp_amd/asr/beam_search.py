@@ -14,6 +14,10 @@ the CTC prefix kernel (esp_ctc_prefix_score: a thread per (hypothesis, candidate
 step; the hypothesis bookkeeping (tiny) happens on the host after one device->host copy.
 The decoder is re-run on the full prefix each step (the reference caches layer outputs in
 forward_one_step; the last position's output is the same function of the prefix).
+
+BatchBeamSearch (below) is the reference's batch search on the cached one-step decoder
+(TransformerDecoder.batch_score: only the newest position is computed, the memory's source-attention
+K/V are projected once), for one utterance or for several in lockstep (forward_batch).
 """
 import math
 from itertools import chain
@@ -213,3 +217,134 @@ class BeamSearch:
         if not nbest:
             return [] if minlenratio < 0.1 else self.forward(x, maxlenratio, max(0.0, minlenratio - 0.1))
         return nbest
+
+
+class BatchBeamSearch(BeamSearch):
+    """The reference's BatchBeamSearch (espnet/nets/batch_beam_search.py:85-340 with the batch CTC scorer,
+    scorers/ctc.py:88-140 + CTCPrefixScoreTH), which is what its Speech2Text runs, on the cached one-step decoder.
+
+    Batch semantics, where they differ from BeamSearch above: the top `beam` are taken over the flattened
+    (hypothesis x vocabulary) weighted scores of an utterance; the partial (CTC) scorer returns a full-size score
+    row per hypothesis -- the prefix scores on the pre-beam ids, <eos> always scored (whether or not the pre-beam
+    kept it), logzero = -1e10 everywhere else -- which is added with its weight; ended hypotheses get no
+    final_score.  post_process / end_detect / maxlen follow BeamSearch.forward.
+
+    forward_batch runs U utterances in lockstep: every output step is ONE decoder step over the running rows
+    of all utterances (TransformerDecoder.batch_score on a DecoderCache and the memory projected once), ONE
+    esp_ctc_prefix_score_batch launch and ONE device->host copy (parent row, token and scores of the U x beam
+    selected entries); the host keeps the token sequences and decides what ended.  Each utterance has its own
+    maxlen and end_detect, finishes on its own, and its rows are then dropped.  Rows stay sorted by utterance.
+    """
+
+    LOGZERO = -10000000000.0
+
+    def forward(self, x: torch.Tensor, maxlenratio: float = 0.0, minlenratio: float = 0.0) -> List[Hypothesis]:
+        return self.forward_batch(x.unsqueeze(0), [x.shape[0]], maxlenratio, minlenratio)[0]
+
+    def forward_batch(self, xs_pad: torch.Tensor, xlens, maxlenratio: float = 0.0,
+                      minlenratio: float = 0.0) -> List[List[Hypothesis]]:
+        """xs_pad (U, Tmax, D) encoder outputs, xlens (U,) their lengths -> one n-best list per utterance."""
+        U, Tmax, _ = xs_pad.shape
+        dev, V, beam = xs_pad.device, self.n_vocab, self.beam_size
+        xlens = [int(t) for t in xlens]
+        assert len(xlens) == U and all(1 <= t <= Tmax for t in xlens), (xlens, xs_pad.shape)
+        maxlen = [t if maxlenratio == 0 else max(1, int(maxlenratio * t)) for t in xlens]
+        dec = self.full_scorers["decoder"].decoder if "decoder" in self.full_scorers else None
+        ctc = self.part_scorers.get("ctc")
+        names = list(chain(self.full_scorers, self.part_scorers))
+        ended: List[List[Hypothesis]] = [[] for _ in range(U)]
+        self.finish_step = [-1] * U  # the output step at which each utterance's search ended
+        self.steps = 0
+        with torch.no_grad():
+            xs_pad = xs_pad.to(torch.float32).contiguous()
+            mem = dec.prepare_memory(xs_pad, xlens) if dec is not None else None
+            cache = dec.init_cache(U) if dec is not None else None
+            if ctc is not None:
+                lp = ctc.ctc.log_softmax(xs_pad).contiguous()
+                tlen = K.h2d(torch.tensor(xlens, dtype=torch.int32), dev)
+                r = torch.stack([K.ctc_prefix_init(lp[u], ctc.blank) for u in range(U)])  # (N, Tmax, 2)
+                s_prev = torch.zeros(U, dtype=torch.float32, device=dev)
+            # running rows, sorted by utterance: host token sequences / utterance ids, device scores
+            ys = np.full((U, 1), self.sos, dtype=np.int64)
+            utt = np.arange(U, dtype=np.int32)
+            score = torch.zeros(U, dtype=torch.float32, device=dev)
+            scores = {k: torch.zeros(U, dtype=torch.float32, device=dev) for k in names}
+            for i in range(max(maxlen)):
+                N = ys.shape[0]
+                active, counts = np.unique(utt, return_counts=True)  # ascending: the row order
+                A = len(active)
+                start = np.concatenate([[0], np.cumsum(counts)[:-1]])
+                utt_dev = K.h2d(torch.from_numpy(utt), dev)
+                # full scorers
+                full = {}
+                weighted = torch.zeros(N, V, dtype=torch.float32, device=dev)
+                for k in self.full_scorers:
+                    if k == "decoder":
+                        full[k], cache = dec.batch_score(torch.from_numpy(ys), cache, (mem, utt))
+                    else:
+                        full[k] = torch.ones(N, V, dtype=torch.float32, device=dev)
+                    weighted += self.weights[k] * full[k]
+                # partial scorer on the pre-beam ids (+ <eos>), as a full-size score row
+                if ctc is not None:
+                    if self.do_pre_beam:
+                        pre = weighted if self.pre_beam_score_key == "full" else full[self.pre_beam_score_key]
+                        cands = torch.cat([torch.topk(pre, self.pre_beam_size, dim=1)[1],
+                                           torch.full((N, 1), self.eos, dtype=torch.int64, device=dev)], 1).contiguous()
+                    else:
+                        cands = torch.arange(V, device=dev).expand(N, V).contiguous()
+                    last = K.h2d(torch.from_numpy(np.ascontiguousarray(ys[:, -1])), dev)
+                    psi, r_new = K.ctc_prefix_score_batch(lp, tlen, utt_dev, r, last, i, cands, ctc.blank, ctc.eos)
+                    psi_full = torch.full((N, V), self.LOGZERO, dtype=torch.float32, device=dev).scatter_(1, cands, psi)
+                    part = psi_full - s_prev[:, None]
+                    weighted += self.weights["ctc"] * part
+                weighted += score[:, None]
+                # top `beam` of every utterance over its flattened (row x vocabulary) scores
+                slot = np.concatenate([a * beam + np.arange(c) for a, c in enumerate(counts)])
+                padded = torch.full((A * beam, V), -float("inf"), dtype=torch.float32, device=dev)
+                padded[K.h2d(torch.from_numpy(slot), dev)] = weighted
+                vals, flat = padded.view(A, beam * V).topk(beam, dim=1)
+                parent = (torch.div(flat, V, rounding_mode="floor")
+                          + K.h2d(torch.from_numpy(start), dev)[:, None]).reshape(-1)
+                tok = (flat % V).reshape(-1)
+                new_scores = {k: scores[k][parent] + (part if k == "ctc" else full[k])[parent, tok] for k in names}
+                # the one device->host copy of the step
+                host = torch.stack([parent.double(), tok.double(), vals.reshape(-1).double()]
+                                   + [new_scores[k].double() for k in names]).cpu().numpy()
+                self.steps += 1
+                h_parent, h_tok = host[0].astype(np.int64), host[1].astype(np.int64)
+                keep = []
+                for a, u in enumerate(active):
+                    remained = 0
+                    for e in range(a * beam, (a + 1) * beam):
+                        y = list(ys[h_parent[e]]) + [int(h_tok[e])]
+                        if i == maxlen[u] - 1:
+                            y.append(self.eos)
+                        if y[-1] == self.eos:
+                            ended[u].append(Hypothesis(yseq=torch.tensor(y, dtype=torch.int64), score=float(host[2, e]),
+                                                       scores={k: float(host[3 + j, e]) for j, k in enumerate(names)},
+                                                       states={}))
+                        else:
+                            keep.append(e)
+                            remained += 1
+                    if (maxlenratio == 0.0 and end_detect([h.asdict() for h in ended[u]], i)) or remained == 0:
+                        keep = keep[: len(keep) - remained]
+                        self.finish_step[u] = i
+                if not keep:
+                    break
+                keep = np.asarray(keep, dtype=np.int64)
+                ys = np.concatenate([ys[h_parent[keep]], h_tok[keep, None]], 1)
+                utt = np.ascontiguousarray(active[keep // beam].astype(np.int32))
+                keep_dev = K.h2d(torch.from_numpy(keep), dev)
+                parent, tok = parent[keep_dev], tok[keep_dev]
+                score = vals.reshape(-1)[keep_dev]
+                scores = {k: v[keep_dev] for k, v in new_scores.items()}
+                if cache is not None:
+                    cache.reorder(parent)
+                if ctc is not None:
+                    # the candidate slot of the chosen token (a duplicate <eos> slot holds the same state; a
+                    # token outside the candidates can only be chosen at logzero: slot 0, as the reference does)
+                    slotmap = torch.full((N, V), -1, dtype=torch.int64, device=dev)
+                    slotmap.scatter_(1, cands, torch.arange(cands.shape[1], device=dev).expand_as(cands))
+                    r = r_new[parent, slotmap[parent, tok].clamp_(min=0)].contiguous()
+                    s_prev = psi_full[parent, tok]
+        return [sorted(e, key=lambda h: h.score, reverse=True) for e in ended]

@@ -6,12 +6,18 @@ LN -> source MHA over the encoder output -> +res; LN -> FFN(ReLU) -> +res]
 Masks: tgt (j < ys_in_len_b and j <= i), memory (j < hlen_b) — applied inside the softmax
 kernel, nothing materialised.  Explicit backward; the memory gradient of every layer is
 accumulated into one dhs buffer.
+
+Inference also has the reference's incremental interface (transformer_decoder.py:147-229):
+prepare_memory / forward_one_step / score / batch_score compute only the newest position of every
+decode row, over a preallocated self-attention K/V cache (DecoderCache) and the memory K/V projected
+once per utterance (PreparedMemory), with the single-query attention kernel esp_decode_attn.
 """
 from __future__ import annotations
 
 import math
-from typing import Tuple
+from typing import Any, NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -54,6 +60,90 @@ class DecoderLayer(nn.Module):
         self.norm2.bwd(c.ln2, self.src_attn.bwd(c.src, d, dmem), d)
         self.norm1.bwd(c.ln1, self.self_attn.bwd(c.sa, d), d)
         return d
+
+
+class PreparedMemory:
+    """The encoder memory of U utterances as every decoder layer's source attention reads it: kv
+    (num_blocks, U*T, 2D) fp32, layer l's linear_k | linear_v projection of the (U, T, D) memory, computed once
+    (TransformerDecoder.prepare_memory).  hlens: the utterances' encoder lengths (host int32)."""
+
+    def __init__(self, kv: torch.Tensor, hlens: np.ndarray, U: int, T: int):
+        self.kv, self.hlens, self.U, self.T = kv, hlens, U, T
+        self._index = (None, None)
+
+    def index(self, rows: np.ndarray) -> "K.DecodeIndex":
+        """The (src, klen) launch index of decode rows reading utterances `rows` (kept while rows repeat)."""
+        key = rows.tobytes()
+        if self._index[0] != key:
+            if rows.size and (rows.min() < 0 or rows.max() >= self.U):
+                raise ValueError(f"PreparedMemory: row -> utterance index outside [0, {self.U})")
+            self._index = (key, K.DecodeIndex(rows, self.hlens[rows], self.kv.device))
+        return self._index[1]
+
+
+class DecoderCache:
+    """Self-attention cache of the one-step decoder: buf (num_blocks, rows, positions, 2D) fp32 holds, for every
+    layer, each decode row's prefix keys (columns [0, D)) and values ([D, 2D)) -- not the layer outputs the
+    reference caches; the state is opaque to a search, which only passes it back and reorders it.  Preallocated;
+    rows and positions grow by doubling; reorder(index) keeps row index[i] as row i (the parent selection
+    after pruning; an index may repeat and may be longer than the current row count)."""
+
+    def __init__(self, num_blocks: int, D: int, device, rows: int = 1, capacity: int = 32):
+        self.buf = torch.empty(num_blocks, max(1, rows), max(1, capacity), 2 * D, dtype=torch.float32, device=device)
+        self.n = rows   # decode rows in use
+        self.len = 0    # positions stored per row
+
+    @property
+    def row_capacity(self) -> int:
+        return self.buf.shape[1]
+
+    @property
+    def capacity(self) -> int:
+        return self.buf.shape[2]
+
+    def ensure(self, rows: int, length: int):
+        nl, R, C, W = self.buf.shape
+        if rows <= R and length <= C:
+            return
+        while R < rows:
+            R *= 2
+        while C < length:
+            C *= 2
+        new = torch.empty(nl, R, C, W, dtype=torch.float32, device=self.buf.device)
+        if self.n and self.len:
+            new[:, :self.n, :self.len] = self.buf[:, :self.n, :self.len]
+        self.buf = new
+
+    def _index(self, index) -> torch.Tensor:
+        if not torch.is_tensor(index):
+            index = K.h2d(torch.as_tensor(np.asarray(index, dtype=np.int64)), self.buf.device)
+        return index.to(device=self.buf.device, dtype=torch.int64)
+
+    def reorder(self, index) -> "DecoderCache":
+        index = self._index(index)
+        n = int(index.numel())
+        g = self.buf[:, index, :self.len] if self.len else None  # gathered before the rows are overwritten
+        self.ensure(n, self.len)
+        if g is not None:
+            self.buf[:, :n, :self.len] = g
+        self.n = n
+        return self
+
+    def select(self, index) -> "DecoderCache":
+        """A new cache holding rows `index` of this one (this one is left as it is)."""
+        index = self._index(index)
+        nl, _, C, W = self.buf.shape
+        out = DecoderCache(nl, W // 2, self.buf.device, rows=int(index.numel()), capacity=C)
+        if self.len:
+            out.buf[:, :, :self.len] = self.buf[:, index, :self.len]
+        out.len = self.len
+        return out
+
+
+class RowState(NamedTuple):
+    """One hypothesis' decoder state in the list form of batch_score: row `row` of `cache`."""
+    cache: DecoderCache
+    row: int
 
 
 class TransformerDecoder(AbsDecoder):
@@ -131,3 +221,156 @@ class TransformerDecoder(AbsDecoder):
                                          Seeds(draw_seed()), self.training)
         B, L = ys_in_pad.shape
         return logits.view(B, L, -1), ys_in_lens
+
+    # ------------------------------------------------------------------ incremental inference
+    def _eval_only(self, what: str):
+        if self.training:
+            raise RuntimeError(f"TransformerDecoder.{what}: the one-step decoder is inference only (call .eval())")
+
+    def init_cache(self, rows: int = 1, capacity: int = 32) -> DecoderCache:
+        """An empty self-attention cache for `rows` decode rows with room for `capacity` positions."""
+        return DecoderCache(len(self.decoders), self.D, self.embed[0].weight.device, rows=rows, capacity=capacity)
+
+    def prepare_memory(self, hs_pad: torch.Tensor, hlens) -> PreparedMemory:
+        """hs_pad (U, T, D), hlens (U,) -> every layer's source-attention keys and values of the memory, one
+        linear_k | linear_v GEMM per layer over the U*T rows.  Computed once per batch of utterances."""
+        self._eval_only("prepare_memory")
+        U, T, D = hs_pad.shape
+        hl = np.asarray(torch.as_tensor(hlens).cpu(), dtype=np.int32).reshape(-1)
+        if hl.shape[0] != U or hl.min() < 1 or hl.max() > T:
+            raise ValueError(f"prepare_memory: hlens {hl.tolist()} for a memory of shape {tuple(hs_pad.shape)}")
+        with torch.no_grad():
+            mem = hs_pad.to(torch.float32).contiguous().view(U * T, D)
+            kv = torch.empty(len(self.decoders), U * T, 2 * D, dtype=torch.float32, device=mem.device)
+            for l, layer in enumerate(self.decoders):
+                w, b = layer.src_attn._w(("linear_k", "linear_v"))
+                K.linear_fwd(mem, w, b, kv[l])
+        return PreparedMemory(kv, hl, U, T)
+
+    def _resolve_memory(self, memory, N: int) -> Tuple[PreparedMemory, np.ndarray]:
+        rows = None
+        if isinstance(memory, (tuple, list)):
+            memory, rows = memory
+        if torch.is_tensor(memory):  # plain (N, T, D) memory: projected on the spot (correct, slow)
+            if memory.dim() == 2:
+                memory = memory.unsqueeze(0)
+            memory = self.prepare_memory(memory, [memory.shape[1]] * memory.shape[0])
+        if rows is None:
+            if memory.U not in (1, N):
+                raise ValueError(f"{N} decode rows over a memory of {memory.U} utterances need a row -> utterance index")
+            rows = np.arange(N) if memory.U == N else np.zeros(N)
+        elif torch.is_tensor(rows):
+            rows = rows.cpu().numpy()
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        if rows.shape[0] != N:
+            raise ValueError(f"row -> utterance index of {rows.shape[0]} entries for {N} decode rows")
+        return memory, rows
+
+    def _step(self, tok: torch.Tensor, mem: PreparedMemory, rows: np.ndarray, cache: DecoderCache,
+              want_logp: bool = True) -> Optional[torch.Tensor]:
+        """One position (cache.len) of every decode row: tok (N,) int64 device, the row's token there."""
+        N, D, pos = tok.shape[0], self.D, cache.len
+        H = self.decoders[0].self_attn.h
+        dk = D // H
+        dev = tok.device
+        cache.ensure(N, pos + 1)
+        pe = pos_table("abs", max(512, 1 << pos.bit_length()), D, dev)
+        x = torch.empty(N, D, dtype=torch.float32, device=dev)
+        K.embed_fwd(tok, self.embed[0].weight, pe[pos:pos + 1], x, 1, math.sqrt(D), 0.0, 0)
+        self_idx = K.DecodeIndex(np.arange(N), pos + 1, dev)
+        src_idx = mem.index(rows)
+        seeds = Seeds(0)
+        R, C = cache.row_capacity, cache.capacity
+        for l, layer in enumerate(self.decoders):
+            sa, ca = layer.self_attn, layer.src_attn
+            h, _ = layer.norm1.fwd(x)
+            w, b = sa._w(("linear_q", "linear_k", "linear_v"))
+            qkv = empty(N, 3 * D, like=x)
+            K.linear_fwd(h, w, b, qkv)
+            cb = cache.buf[l]
+            cb[:N, pos] = qkv[:, D:]
+            ctx = empty(N, D, like=x)
+            K.decode_attn(qkv, 3 * D, 0, cb, 2 * D, C * 2 * D, 0, cb, 2 * D, C * 2 * D, D, ctx, D, 0, self_idx, H, dk,
+                          R, C)
+            x = sa.linear_out.fwd(ctx, R=x, beta=1.0)
+            h, _ = layer.norm2.fwd(x)
+            q = ca.linear_q.fwd(h)
+            kv = mem.kv[l]
+            K.decode_attn(q, D, 0, kv, 2 * D, mem.T * 2 * D, 0, kv, 2 * D, mem.T * 2 * D, D, ctx, D, 0, src_idx, H, dk,
+                          mem.U, mem.T)
+            x = ca.linear_out.fwd(ctx, R=x, beta=1.0)
+            h, _ = layer.norm3.fwd(x)
+            x, _ = layer.feed_forward.fwd(h, x, 1.0, 0.0, seeds, False)
+        cache.len = pos + 1
+        if not want_logp:
+            return None
+        y, _ = self.after_norm.fwd(x)
+        logits = self.output_layer.fwd(y)
+        logp = torch.empty_like(logits)
+        K.log_softmax(logits, logp, N, logits.shape[1])
+        return logp
+
+    def forward_one_step(self, tgt: torch.Tensor, tgt_mask, memory, cache: Optional[DecoderCache] = None
+                         ) -> Tuple[torch.Tensor, DecoderCache]:
+        """tgt (N, L) prefixes -> (log p(. | prefix) (N, V), cache); only position L-1 is computed.
+
+        tgt_mask is accepted for the reference's signature and ignored: the step is causal by construction
+        (position L-1 attends the L cached positions).  memory: a PreparedMemory (U = N or U = 1), a pair
+        (PreparedMemory, row -> utterance index), or a plain (N, T, D) tensor, which is projected on the spot
+        (correct but slow).  cache: what an earlier step returned, its rows already in tgt's order
+        (DecoderCache.reorder); None (or an empty cache) computes the earlier positions one by one first."""
+        self._eval_only("forward_one_step")
+        N, L = tgt.shape
+        with torch.no_grad():
+            mem, rows = self._resolve_memory(memory, N)
+            dev = mem.kv.device
+            if cache is None:
+                cache = self.init_cache(N)
+            if cache.len == 0:
+                cache.n = N
+            if cache.n != N or cache.len > L - 1:
+                raise ValueError(f"forward_one_step: cache of {cache.n} rows x {cache.len} positions for tgt {N} x {L}")
+            tgt = K.h2d(tgt.to(torch.int64), dev)
+            while cache.len < L - 1:
+                self._step(tgt[:, cache.len].contiguous(), mem, rows, cache, want_logp=False)
+            return self._step(tgt[:, L - 1].contiguous(), mem, rows, cache), cache
+
+    def score(self, ys: torch.Tensor, state: Optional[DecoderCache], x) -> Tuple[torch.Tensor, DecoderCache]:
+        """ys (L,), state (None at first), x (T, D) memory or a PreparedMemory of one utterance -> (logp (V,), state)."""
+        logp, state = self.forward_one_step(ys.unsqueeze(0), None, x, cache=state)
+        return logp[0], state
+
+    def batch_score(self, ys: torch.Tensor, states, xs) -> Tuple[torch.Tensor, Any]:
+        """ys (N, L), states, xs -> (logp (N, V), states).  states: a DecoderCache whose rows are ys' rows (or None
+        at the first step) -- returned as a DecoderCache; or the reference's list form, one entry per hypothesis
+        (None at first, then the RowState entries an earlier call returned, in any order and from any call) --
+        returned as a list.  The list form gathers the rows into a new cache (one gather per distinct source
+        cache, no loop over hypotheses on the device).  xs as forward_one_step's memory."""
+        self._eval_only("batch_score")
+        if states is None or isinstance(states, DecoderCache):
+            return self.forward_one_step(ys, None, xs, cache=states)
+        states = list(states)
+        if len(states) != ys.shape[0]:
+            raise ValueError(f"batch_score: {len(states)} states for {ys.shape[0]} prefixes")
+        if all(s is None for s in states):
+            cache = None
+        else:
+            if any(s is None for s in states):
+                raise ValueError("batch_score: a mix of empty and non-empty states")
+            first = states[0].cache
+            if all(s.cache is first for s in states):
+                cache = first.select([s.row for s in states])
+            else:
+                if len({s.cache.len for s in states}) != 1:
+                    raise ValueError("batch_score: states of different prefix lengths")
+                cache = self.init_cache(len(states), capacity=max(s.cache.capacity for s in states))
+                cache.len = first.len
+                by_cache = {}
+                for i, s in enumerate(states):
+                    by_cache.setdefault(id(s.cache), (s.cache, [], []))
+                    by_cache[id(s.cache)][1].append(i)
+                    by_cache[id(s.cache)][2].append(s.row)
+                for c, dst, src in by_cache.values():
+                    cache.buf[:, cache._index(dst), :cache.len] = c.buf[:, c._index(src), :cache.len]
+        logp, cache = self.forward_one_step(ys, None, xs, cache=cache)
+        return logp, [RowState(cache, i) for i in range(ys.shape[0])]

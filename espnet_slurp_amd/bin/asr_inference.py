@@ -5,13 +5,19 @@ asr/beam_search.py with the reference's weights: decoder 1 - ctc_weight, ctc ctc
 length_bonus penalty; pre-beam on the "full" scores unless ctc_weight == 1.0.
 Tokenizers: "bpe" (sentencepiece model file, as the SLURP recipes use) and "char";
 ids2tokens by the model's token_list.  LM / n-gram / transducer / streaming are out of scope.
+
+batch_search=True runs the reference Speech2Text's own search instead, BatchBeamSearch (top `beam` over the
+flattened hypothesis x vocabulary scores, <eos> always CTC-scored), on the cached one-step decoder: the
+memory's source-attention K/V are projected once per utterance and every output step computes the newest
+position only.  decode_batch(speeches) encodes several utterances as one padded batch and searches them in
+lockstep (BatchBeamSearch.forward_batch).  The default stays the plain search.
 """
 from typing import List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
-from ..asr.beam_search import BeamSearch, CTCPrefixScorer, DecoderScorer, Hypothesis, LengthBonus
+from ..asr.beam_search import BatchBeamSearch, BeamSearch, CTCPrefixScorer, DecoderScorer, Hypothesis, LengthBonus
 
 
 class CharTokenizer:
@@ -35,7 +41,8 @@ class SentencepiecesTokenizer:
 class Speech2Text:
     def __init__(self, asr_model, token_list: Optional[List[str]] = None, beam_size: int = 20,
                  ctc_weight: float = 0.5, penalty: float = 0.0, nbest: int = 1, maxlenratio: float = 0.0,
-                 minlenratio: float = 0.0, token_type: Optional[str] = None, bpemodel: Optional[str] = None):
+                 minlenratio: float = 0.0, token_type: Optional[str] = None, bpemodel: Optional[str] = None,
+                 batch_search: bool = False):
         asr_model.eval()
         self.asr_model = asr_model
         self.device = asr_model.flat.flat.device
@@ -45,10 +52,12 @@ class Speech2Text:
                        ctc=CTCPrefixScorer(asr_model.ctc, eos=asr_model.eos, blank=asr_model.blank_id),
                        length_bonus=LengthBonus())
         weights = dict(decoder=1.0 - ctc_weight, ctc=ctc_weight, length_bonus=penalty)
-        self.beam_search = BeamSearch(scorers=scorers, weights=weights, beam_size=beam_size,
-                                      vocab_size=len(self.token_list), sos=asr_model.sos, eos=asr_model.eos,
-                                      token_list=self.token_list,
-                                      pre_beam_score_key=None if ctc_weight == 1.0 else "full")
+        kw = dict(scorers=scorers, weights=weights, beam_size=beam_size, vocab_size=len(self.token_list),
+                  sos=asr_model.sos, eos=asr_model.eos, token_list=self.token_list,
+                  pre_beam_score_key=None if ctc_weight == 1.0 else "full")
+        self.batch_search = batch_search
+        self.batch_beam_search = BatchBeamSearch(**kw)  # decode_batch's search, and __call__'s with batch_search
+        self.beam_search = self.batch_beam_search if batch_search else BeamSearch(**kw)
         self.maxlenratio, self.minlenratio, self.nbest = maxlenratio, minlenratio, nbest
         if token_type == "bpe":
             self.tokenizer = SentencepiecesTokenizer(bpemodel)
@@ -70,7 +79,27 @@ class Speech2Text:
     def __call__(self, speech: Union[torch.Tensor, np.ndarray]) -> List[Tuple[Optional[str], List[str], List[int],
                                                                                 Hypothesis]]:
         enc = self.encode(speech)
-        hyps = self.beam_search.forward(enc, self.maxlenratio, self.minlenratio)[: self.nbest]
+        return self._results(self.beam_search.forward(enc, self.maxlenratio, self.minlenratio))
+
+    @torch.no_grad()
+    def decode_batch(self, speeches: list) -> List[List[Tuple[Optional[str], List[str], List[int], Hypothesis]]]:
+        """Several utterances at once: one padded-batch encode, one lockstep BatchBeamSearch.forward_batch (whatever
+        batch_search says); one result list per utterance, each in __call__'s tuple form.
+
+        The padded-batch encode follows the reference's batch behaviour at utterance ends (the encoder treats a
+        shorter utterance's padding as it does in a training batch), so its encoder outputs, and with them the
+        scores, are not bit-equal to single-utterance encodes."""
+        sp = [torch.as_tensor(s).to(torch.float32) for s in speeches]
+        lengths = torch.tensor([s.shape[0] for s in sp], dtype=torch.int64)
+        pad = torch.zeros((len(sp), int(lengths.max())) + tuple(sp[0].shape[1:]), dtype=torch.float32)
+        for i, s in enumerate(sp):
+            pad[i, : s.shape[0]] = s
+        enc, enc_lens = self.asr_model.encode(pad.to(self.device), lengths, sl_cpu=lengths)
+        nbests = self.batch_beam_search.forward_batch(enc, [int(t) for t in enc_lens], self.maxlenratio, self.minlenratio)
+        return [self._results(h) for h in nbests]
+
+    def _results(self, hyps):
+        hyps = hyps[: self.nbest]
         out = []
         for h in hyps:
             token_int = [t for t in h.yseq[1:-1].tolist() if t != 0]

@@ -1,0 +1,135 @@
+// Single-query attention for the cached decoder step (beam search inference; the reference computes the
+// same thing through MultiHeadedAttention on a one-row query, transformer/attention.py:55-114, from
+// TransformerDecoder.forward_one_step, espnet2/asr/decoder/transformer_decoder.py:147-190).
+//
+//   out[n, h] = softmax(q[n, h] . K[src[n], :klen[n], h] / sqrt(d_k)) . V[src[n], :klen[n], h]
+//
+// N decode rows, one query vector each.  Self-attention: src[n] = n, klen = the prefix length, K / V the
+// row's cached prefix.  Source attention: src[n] = the row's utterance, klen = that utterance's encoder
+// length, K / V the utterance's projected memory (many rows share one src).
+//
+// Layout of the work: one wave per (row, head), four waves to a block.  A lane owns one key of each
+// 64-key chunk: it reads that key's d_k floats (float4 loads; a lane reads whole 64 / 128 / 256-byte
+// runs), forms the score, and the wave reduces the chunk's maximum (online softmax: running maximum m,
+// per-lane partial denominators l and per-lane partial outputs acc[d_k], all rescaled by the wave-uniform
+// exp(m_old - m_new)).  The lane then reads its key's V row and adds p * V.  After the last chunk l and
+// the d_k accumulators are summed across the wave once.  Keys at or beyond klen[n] are never read: their
+// lanes skip both loads and carry p = 0.  All arithmetic is fp32.
+// Rows with the same src read the same K / V bytes; this version leaves that sharing to the L2 (the
+// rows arrive sorted by utterance, so the waves of one utterance run close together in time).
+#include "common.h"
+
+namespace {
+
+constexpr int kDecodeChunk = 64;  // keys per online-softmax step: one per lane
+
+template <int DK>
+__global__ void __launch_bounds__(256)
+decode_attn_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ k, long ldk, long sk,
+                   const float* __restrict__ v, long ldv, long sv, float* __restrict__ out, long ldo,
+                   const int* __restrict__ src, const int* __restrict__ klen, int N, int H, float inv_sqrt_dk) {
+  const int lane = threadIdx.x & 63;
+  const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= (long)N * H) return;  // wave-uniform
+  const int n = (int)(item / H), h = (int)(item - (long)n * H);
+  const int s = src[n], len = klen[n];
+  float qr[DK];
+  {
+    const float4* qp = reinterpret_cast<const float4*>(q + (long)n * ldq + (long)h * DK);
+#pragma unroll
+    for (int d = 0; d < DK / 4; ++d) {
+      const float4 t = qp[d];
+      qr[4 * d] = t.x, qr[4 * d + 1] = t.y, qr[4 * d + 2] = t.z, qr[4 * d + 3] = t.w;
+    }
+  }
+  const float* kp = k + (long)s * sk + (long)h * DK;
+  const float* vp = v + (long)s * sv + (long)h * DK;
+  float m = -INFINITY, l = 0.f;
+  float acc[DK];
+#pragma unroll
+  for (int d = 0; d < DK; ++d) acc[d] = 0.f;
+  for (int j0 = 0; j0 < len; j0 += kDecodeChunk) {
+    const int j = j0 + lane;
+    const bool live = j < len;
+    float sc = -INFINITY;
+    if (live) {
+      const float4* kr = reinterpret_cast<const float4*>(kp + (long)j * ldk);
+      float dot = 0.f;
+#pragma unroll
+      for (int d = 0; d < DK / 4; ++d) {
+        const float4 t = kr[d];
+        dot = fmaf(qr[4 * d], t.x, dot);
+        dot = fmaf(qr[4 * d + 1], t.y, dot);
+        dot = fmaf(qr[4 * d + 2], t.z, dot);
+        dot = fmaf(qr[4 * d + 3], t.w, dot);
+      }
+      sc = dot * inv_sqrt_dk;
+    }
+    // lane 0 of every chunk is live (j0 < len), so mn is finite; exp(-inf) = 0 on the first chunk
+    const float mn = fmaxf(m, esp::wave_max(sc));
+    const float a = __expf(m - mn);
+    const float p = live ? __expf(sc - mn) : 0.f;
+    l = l * a + p;
+    if (live) {
+      const float4* vr = reinterpret_cast<const float4*>(vp + (long)j * ldv);
+#pragma unroll
+      for (int d = 0; d < DK / 4; ++d) {
+        const float4 t = vr[d];
+        acc[4 * d] = fmaf(p, t.x, acc[4 * d] * a);
+        acc[4 * d + 1] = fmaf(p, t.y, acc[4 * d + 1] * a);
+        acc[4 * d + 2] = fmaf(p, t.z, acc[4 * d + 2] * a);
+        acc[4 * d + 3] = fmaf(p, t.w, acc[4 * d + 3] * a);
+      }
+    } else {
+#pragma unroll
+      for (int d = 0; d < DK; ++d) acc[d] *= a;
+    }
+    m = mn;
+  }
+  const float inv_l = 1.f / esp::wave_sum(l);
+  float o = 0.f;  // lane d keeps column d
+#pragma unroll
+  for (int d = 0; d < DK; ++d) {
+    const float t = esp::wave_sum(acc[d]);
+    if (lane == d) o = t;
+  }
+  if (lane < DK) out[(long)n * ldo + (long)h * DK + lane] = o * inv_l;
+}
+
+}  // namespace
+
+ESP_API int esp_decode_attn(const float* q, long ldq, long qoff, const float* k, long ldk, long sk, long koff,
+                            const float* v, long ldv, long sv, long voff, float* out, long ldo, long ooff,
+                            const int* idx_host, const int* idx_dev, int N, int H, int dk, int nsrc, int Tk,
+                            void* stream) {
+  ESP_ARG_CHECK(dk == 16 || dk == 32 || dk == 64, "esp_decode_attn: d_k %d not supported (16, 32, 64)", dk);
+  ESP_ARG_CHECK(N >= 1 && H >= 1 && nsrc >= 1 && Tk >= 1 && (long)N * H < (1L << 31),
+                "esp_decode_attn: bad sizes N=%d H=%d nsrc=%d Tk=%d", N, H, nsrc, Tk);
+  ESP_ARG_CHECK(q && k && v && out && idx_host && idx_dev, "esp_decode_attn: null argument");
+  const long w = (long)H * dk;
+  ESP_ARG_CHECK(qoff >= 0 && koff >= 0 && voff >= 0 && ooff >= 0 && ldq >= qoff + w && ldk >= koff + w &&
+                    ldv >= voff + w && ldo >= ooff + w,
+                "esp_decode_attn: a row (offset + H*d_k) does not fit its leading dimension");
+  ESP_ARG_CHECK(sk >= 0 && sv >= 0 && (nsrc == 1 || (sk >= (long)Tk * ldk && sv >= (long)Tk * ldv)),
+                "esp_decode_attn: source stride smaller than Tk rows");
+  ESP_ARG_CHECK(!((ldq | qoff | ldk | sk | koff | ldv | sv | voff) & 3) &&
+                    !(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15),
+                "esp_decode_attn: q / K / V need 16-byte aligned rows (pointers, strides and offsets %% 4 floats)");
+  for (int n = 0; n < N; ++n) {
+    const int s = idx_host[n], len = idx_host[N + n];
+    ESP_ARG_CHECK(s >= 0 && s < nsrc, "esp_decode_attn: src[%d] = %d outside [0, %d)", n, s, nsrc);
+    ESP_ARG_CHECK(len >= 1 && len <= Tk, "esp_decode_attn: klen[%d] = %d outside [1, %d]", n, len, Tk);
+  }
+  const float inv = 1.0f / sqrtf((float)dk);
+  const dim3 grid((unsigned)(((long)N * H + 3) / 4)), block(256);
+  const hipStream_t st = (hipStream_t)stream;
+#define ESP_DECODE_ATTN_LAUNCH(DK)                                                                              \
+  hipLaunchKernelGGL(decode_attn_kernel<DK>, grid, block, 0, st, q + qoff, ldq, k + koff, ldk, sk, v + voff, ldv, \
+                     sv, out + ooff, ldo, idx_dev, idx_dev + N, N, H, inv)
+  if (dk == 16) ESP_DECODE_ATTN_LAUNCH(16);
+  else if (dk == 32) ESP_DECODE_ATTN_LAUNCH(32);
+  else ESP_DECODE_ATTN_LAUNCH(64);
+#undef ESP_DECODE_ATTN_LAUNCH
+  ESP_CHECK_LAUNCH("esp_decode_attn");
+  return 0;
+}

@@ -537,3 +537,70 @@ ESP_API int esp_ctc_prefix_score(const float* lp, int T, int V, const float* r_p
   ESP_CHECK_LAUNCH("esp_ctc_prefix_score");
   return 0;
 }
+
+// The same recursion for the hypotheses of several utterances in one launch (BatchBeamSearch.forward_batch):
+// lp (U, Tmax, V), hypothesis hy belongs to utterance utt[hy] and uses its first tlen[utt[hy]] frames; states
+// are (Tmax, 2) rows.  Frames at or beyond the utterance's length do not contribute: the recursion and the
+// <eos> score end at tlen - 1, and the state rows past it are written as logzero.  A hypothesis whose
+// utterance index, length or label is out of range reads nothing and scores logzero.
+namespace {
+__global__ void ctc_prefix_score_batch_kernel(const float* __restrict__ lp_all, int U, int Tmax, int V,
+                                              const int* __restrict__ tlen, const int* __restrict__ utt,
+                                              const float* __restrict__ r_prev, const long long* __restrict__ last,
+                                              int out_len, const long long* __restrict__ cands, int NH, int C,
+                                              int blank, int eos, float* __restrict__ r_new,
+                                              float* __restrict__ log_psi) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)NH * C) return;
+  const int hy = (int)(idx / C);
+  const long long cl = cands[idx];
+  const int u = utt[hy];
+  float* rn = r_new + idx * Tmax * 2;
+  for (int t = 0; t < Tmax; ++t) {
+    rn[2 * t] = kLogZero;
+    rn[2 * t + 1] = kLogZero;
+  }
+  const int T = (u >= 0 && u < U) ? tlen[u] : 0;
+  if (T < 1 || T > Tmax || cl < 0 || cl >= V) {
+    log_psi[idx] = kLogZero;
+    return;
+  }
+  const int c = (int)cl;
+  const float* lp = lp_all + (long)u * Tmax * V;
+  const float* rp = r_prev + (long)hy * Tmax * 2;
+  const bool same_as_last = out_len > 0 && cl == last[hy];
+  if (out_len == 0) rn[0] = lp[c];
+  const int start = out_len > 1 ? out_len : 1;
+  float rn0 = rn[2 * (start - 1)], rb0 = rn[2 * (start - 1) + 1];
+  float psi = rn0;
+  for (int t = start; t < T; ++t) {
+    const float phi = same_as_last ? rp[2 * (t - 1) + 1] : logaddexpf_np(rp[2 * (t - 1)], rp[2 * (t - 1) + 1]);
+    const float xc = lp[(long)t * V + c];
+    const float n1 = logaddexpf_np(rn0, phi) + xc;
+    const float b1 = logaddexpf_np(rn0, rb0) + lp[(long)t * V + blank];
+    psi = logaddexpf_np(psi, phi + xc);
+    rn[2 * t] = n1;
+    rn[2 * t + 1] = b1;
+    rn0 = n1;
+    rb0 = b1;
+  }
+  if (c == eos) psi = logaddexpf_np(rp[2 * (T - 1)], rp[2 * (T - 1) + 1]);
+  if (c == blank) psi = kLogZero;
+  log_psi[idx] = psi;
+}
+}  // namespace
+
+ESP_API int esp_ctc_prefix_score_batch(const float* lp, int U, int Tmax, int V, const int* tlen, const int* utt,
+                                       const float* r_prev, const long long* last, int out_len,
+                                       const long long* cands, int NH, int C, int blank, int eos, float* r_new,
+                                       float* log_psi, void* stream) {
+  ESP_ARG_CHECK(U >= 1 && Tmax >= 1 && V >= 1 && NH >= 1 && C >= 1 && out_len >= 0 && out_len <= Tmax &&
+                    blank >= 0 && blank < V && eos >= 0 && eos < V,
+                "esp_ctc_prefix_score_batch: bad sizes U=%d Tmax=%d V=%d NH=%d C=%d out_len=%d", U, Tmax, V, NH, C,
+                out_len);
+  const long n = (long)NH * C;
+  hipLaunchKernelGGL(ctc_prefix_score_batch_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
+                     lp, U, Tmax, V, tlen, utt, r_prev, last, out_len, cands, NH, C, blank, eos, r_new, log_psi);
+  ESP_CHECK_LAUNCH("esp_ctc_prefix_score_batch");
+  return 0;
+}

@@ -1435,6 +1435,53 @@ def ctc_prefix_score(lp, r_prev, last, out_len, cands, blank, eos):
     return psi, r_new
 
 
+def ctc_prefix_score_batch(lp, tlen_i32, utt_i32, r_prev, last, out_len, cands, blank, eos):
+    """ctc_prefix_score for the hypotheses of several utterances in one launch: lp (U, Tmax, V), tlen_i32 (U,)
+    and utt_i32 (NH,) device int32 (frames per utterance, utterance of each hypothesis), r_prev (NH, Tmax, 2),
+    last (NH,) int64, cands (NH, C) int64 -> (log_psi (NH, C), r_new (NH, C, Tmax, 2)).  No host
+    synchronisation: out-of-range labels / utterances score logzero in the kernel."""
+    U, Tmax, V = lp.shape
+    NH, C = cands.shape
+    assert r_prev.shape == (NH, Tmax, 2) and last.shape == (NH,) and utt_i32.shape == (NH,) and tlen_i32.shape == (U,)
+    assert tlen_i32.dtype == torch.int32 and utt_i32.dtype == torch.int32 and cands.dtype == torch.int64
+    assert lp.is_contiguous() and r_prev.is_contiguous() and cands.is_contiguous()
+    _f32(lp, r_prev)
+    r_new = torch.empty(NH, C, Tmax, 2, dtype=torch.float32, device=lp.device)
+    psi = torch.empty(NH, C, dtype=torch.float32, device=lp.device)
+    _native.call("esp_ctc_prefix_score_batch", _p(lp), U, Tmax, V, _p(tlen_i32), _p(utt_i32), _p(r_prev), _p(last),
+                 int(out_len), _p(cands), NH, C, int(blank), int(eos), _p(r_new), _p(psi), _st())
+    return psi, r_new
+
+
+# ----------------------------------------------------------------------------- cached decoder step
+DECODE_ATTN_CHUNK = 64  # keys per online-softmax step of esp_decode_attn (csrc/decode_attn.hip)
+
+
+class DecodeIndex:
+    """The (src, klen) rows of one esp_decode_attn launch, on the host (checked by the launcher) and on the
+    device (read by the kernel): 2N int32, src then klen.  Built once per decoder step and shared by the
+    step's layers."""
+
+    def __init__(self, src, klen, device):
+        import numpy as np
+        src = np.asarray(src, dtype=np.int32).reshape(-1)
+        klen = np.broadcast_to(np.asarray(klen, dtype=np.int32), src.shape)
+        self.host = np.ascontiguousarray(np.stack([src, klen]))
+        self.n = int(src.shape[0])
+        self.dev = h2d(torch.from_numpy(self.host), device)
+
+
+def decode_attn(q, ldq, qoff, k, ldk, sk, koff, v, ldv, sv, voff, out, ldo, ooff, index: DecodeIndex, H, dk, nsrc,
+                Tk):
+    """out[n, h] = softmax(q[n, h] . K[src[n], :klen[n], h] / sqrt(dk)) . V[src[n], :klen[n], h] (esp_decode_attn):
+    q / k / v / out device fp32 tensors addressed by leading dimension, source stride and column offset (in
+    floats), k and v possibly the same fused buffer."""
+    _f32(q, k, v, out)
+    assert index.dev.device == q.device
+    _native.call("esp_decode_attn", _p(q), ldq, qoff, _p(k), ldk, sk, koff, _p(v), ldv, sv, voff, _p(out), ldo, ooff,
+                 index.host.ctypes.data, _p(index.dev), index.n, H, dk, nsrc, Tk, _st())
+
+
 def reserve_workspace(nbytes, device):
     WS.reserve(nbytes, device)
 

@@ -518,6 +518,29 @@ int esp_ctc_prefix_init(const float* lp, int T, int V, int blank, float* r0, voi
 int esp_ctc_prefix_score(const float* lp, int T, int V, const float* r_prev, const long long* last,
                          int out_len, const long long* cands, int NH, int C, int blank, int eos,
                          float* r_new, float* log_psi, void* stream);
+/* ABI 35: esp_ctc_prefix_score for the hypotheses of several utterances in one launch (the lockstep search of
+ * BatchBeamSearch.forward_batch; same recursion, espnet/nets/ctc_prefix_score.py CTCPrefixScoreTH's batch form):
+ * lp (U, Tmax, V), tlen (U) device int32 frames per utterance, utt (NH) device int32 utterance of each
+ * hypothesis; states (NH, Tmax, 2), r_new (NH, C, Tmax, 2).  Frames at or beyond tlen[utt] do not contribute
+ * (the <eos> score is taken at frame tlen - 1; state rows past it are logzero).  A hypothesis whose utterance,
+ * length or candidate label is out of range reads nothing and scores logzero. */
+int esp_ctc_prefix_score_batch(const float* lp, int U, int Tmax, int V, const int* tlen, const int* utt,
+                               const float* r_prev, const long long* last, int out_len, const long long* cands,
+                               int NH, int C, int blank, int eos, float* r_new, float* log_psi, void* stream);
+
+/* ---- ABI 35: single-query attention of the cached decoder step (csrc/decode_attn.hip; replaces
+ * MultiHeadedAttention on a one-row query in TransformerDecoder.forward_one_step,
+ * espnet2/asr/decoder/transformer_decoder.py:147-190):
+ *   out[n, h] = softmax(q[n, h] . K[src[n], :klen[n], h] / sqrt(dk)) . V[src[n], :klen[n], h]
+ * for N rows and H heads, fp32, online softmax over 64-key chunks.  q row n at q + n*ldq + qoff + h*dk; key j
+ * of source sequence s at k + s*sk + j*ldk + koff + h*dk (v alike, so K and V may share one fused buffer); out
+ * row n at out + n*ldo + ooff + h*dk.  idx_host / idx_dev: the same 2N int32 on the host and on the device,
+ * src[0..N) then klen[0..N).  The host copy is checked (0 <= src < nsrc, 1 <= klen <= Tk: status -1), the
+ * kernel reads the device copy; keys at or beyond klen[n] are never read.  dk 16, 32 or 64 (else -1);
+ * q / K / V pointers 16-B aligned, their strides and offsets multiples of 4 floats. */
+int esp_decode_attn(const float* q, long ldq, long qoff, const float* k, long ldk, long sk, long koff,
+                    const float* v, long ldv, long sv, long voff, float* out, long ldo, long ooff,
+                    const int* idx_host, const int* idx_dev, int N, int H, int dk, int nsrc, int Tk, void* stream);
 
 /* ---- workspace sizes.  Every launcher that takes a scratch `work` buffer also takes its size
  * in bytes and fails (status -1, esp_last_error) when it is smaller than the size below, which is
