@@ -3,7 +3,8 @@ espnet/nets/scorers/ctc.py, espnet/nets/scorers/length_bonus.py, e2e_asr_common.
 
 Same search as the reference's BeamSearch (what Speech2Text runs, as BatchBeamSearch, for an
 ESPnet2 ASR model): per running hypothesis the full scorers (decoder log-softmax, length
-bonus) are weighted and summed, the pre-beam keeps int(pre_beam_ratio * beam) labels by that
+bonus, and the neural LM of shallow fusion when one is given: scorer "lm") are weighted and
+summed, the pre-beam keeps int(pre_beam_ratio * beam) labels by that
 sum ("full" key), the CTC prefix scorer scores only those, the hypothesis score is added, the
 top `beam` of every hypothesis are pooled, stably sorted and pruned to `beam`; hypotheses that
 emit <eos> (or reach maxlen) end, and end_detect stops the search when maxlenratio == 0.
@@ -141,8 +142,14 @@ class BeamSearch:
         yseqs = torch.stack([h.yseq for h in running])
         full = {}
         weighted = torch.zeros(NH, V, dtype=torch.float32, device=dev)
+        lm_states = None
         for k, d in self.full_scorers.items():
-            full[k] = d.batch_score(yseqs.to(dev), x) if k == "decoder" else torch.ones(NH, V, device=dev)
+            if k == "decoder":
+                full[k] = d.batch_score(yseqs.to(dev), x)
+            elif k == "lm":  # a neural LM (lm/transformer_lm.py): the reference's list-of-states form
+                full[k], lm_states = d.batch_score(yseqs, [h.states[k] for h in running], None)
+            else:
+                full[k] = torch.ones(NH, V, device=dev)
             weighted += self.weights[k] * full[k]
         if self.do_pre_beam:
             pre = weighted if self.pre_beam_score_key == "full" else full[self.pre_beam_score_key]
@@ -178,6 +185,8 @@ class BeamSearch:
                 for k in self.part_scorers:
                     scores[k] = hyp.scores[k] + float(h_part[k][n, b])
                 states = dict(hyp.states)
+                if lm_states is not None:
+                    states["lm"] = lm_states[n]
                 for k in self.part_scorers:
                     psi, r_new = part_states[k]
                     states[k] = (float(psi[n, pj]), r_new[n, pj])
@@ -230,7 +239,8 @@ class BatchBeamSearch(BeamSearch):
     final_score.  post_process / end_detect / maxlen follow BeamSearch.forward.
 
     forward_batch runs U utterances in lockstep: every output step is ONE decoder step over the running rows
-    of all utterances (TransformerDecoder.batch_score on a DecoderCache and the memory projected once), ONE
+    of all utterances (TransformerDecoder.batch_score on a DecoderCache and the memory projected once), ONE LM step
+    on a second DecoderCache when scorer "lm" is present (TransformerLM.batch_score), ONE
     esp_ctc_prefix_score_batch launch and ONE device->host copy (parent row, token and scores of the U x beam
     selected entries); the host keeps the token sequences and decides what ended.  Each utterance has its own
     maxlen and end_detect, finishes on its own, and its rows are then dropped.  Rows stay sorted by utterance.
@@ -259,6 +269,8 @@ class BatchBeamSearch(BeamSearch):
             xs_pad = xs_pad.to(torch.float32).contiguous()
             mem = dec.prepare_memory(xs_pad, xlens) if dec is not None else None
             cache = dec.init_cache(U) if dec is not None else None
+            lm = self.full_scorers.get("lm")
+            lm_cache = None  # the LM's own K/V cache, reordered and pruned with the decoder's
             if ctc is not None:
                 lp = ctc.ctc.log_softmax(xs_pad).contiguous()
                 tlen = K.h2d(torch.tensor(xlens, dtype=torch.int32), dev)
@@ -281,6 +293,8 @@ class BatchBeamSearch(BeamSearch):
                 for k in self.full_scorers:
                     if k == "decoder":
                         full[k], cache = dec.batch_score(torch.from_numpy(ys), cache, (mem, utt))
+                    elif k == "lm":
+                        full[k], lm_cache = lm.batch_score(torch.from_numpy(ys), lm_cache, None)
                     else:
                         full[k] = torch.ones(N, V, dtype=torch.float32, device=dev)
                     weighted += self.weights[k] * full[k]
@@ -340,6 +354,8 @@ class BatchBeamSearch(BeamSearch):
                 scores = {k: v[keep_dev] for k, v in new_scores.items()}
                 if cache is not None:
                     cache.reorder(parent)
+                if lm_cache is not None:
+                    lm_cache.reorder(parent)
                 if ctc is not None:
                     # the candidate slot of the chosen token (a duplicate <eos> slot holds the same state; a
                     # token outside the candidates can only be chosen at logzero: slot 0, as the reference does)

@@ -146,6 +146,34 @@ class RowState(NamedTuple):
     row: int
 
 
+def merge_row_states(states, n: int, init_cache) -> Optional[DecoderCache]:
+    """The list form of batch_score's states -> one cache whose rows are the list's entries: None when every entry
+    is None (the first step), else the RowState rows gathered into a new cache (one gather per distinct source
+    cache, no loop over hypotheses on the device).  init_cache(rows, capacity=) makes the new cache."""
+    states = list(states)
+    if len(states) != n:
+        raise ValueError(f"batch_score: {len(states)} states for {n} prefixes")
+    if all(s is None for s in states):
+        return None
+    if any(s is None for s in states):
+        raise ValueError("batch_score: a mix of empty and non-empty states")
+    first = states[0].cache
+    if all(s.cache is first for s in states):
+        return first.select([s.row for s in states])
+    if len({s.cache.len for s in states}) != 1:
+        raise ValueError("batch_score: states of different prefix lengths")
+    cache = init_cache(len(states), capacity=max(s.cache.capacity for s in states))
+    cache.len = first.len
+    by_cache = {}
+    for i, s in enumerate(states):
+        by_cache.setdefault(id(s.cache), (s.cache, [], []))
+        by_cache[id(s.cache)][1].append(i)
+        by_cache[id(s.cache)][2].append(s.row)
+    for c, dst, src in by_cache.values():
+        cache.buf[:, cache._index(dst), :cache.len] = c.buf[:, c._index(src), :cache.len]
+    return cache
+
+
 class TransformerDecoder(AbsDecoder):
     def __init__(self, vocab_size: int, encoder_output_size: int, attention_heads: int = 4,
                  linear_units: int = 2048, num_blocks: int = 6, dropout_rate: float = 0.1,
@@ -349,28 +377,6 @@ class TransformerDecoder(AbsDecoder):
         self._eval_only("batch_score")
         if states is None or isinstance(states, DecoderCache):
             return self.forward_one_step(ys, None, xs, cache=states)
-        states = list(states)
-        if len(states) != ys.shape[0]:
-            raise ValueError(f"batch_score: {len(states)} states for {ys.shape[0]} prefixes")
-        if all(s is None for s in states):
-            cache = None
-        else:
-            if any(s is None for s in states):
-                raise ValueError("batch_score: a mix of empty and non-empty states")
-            first = states[0].cache
-            if all(s.cache is first for s in states):
-                cache = first.select([s.row for s in states])
-            else:
-                if len({s.cache.len for s in states}) != 1:
-                    raise ValueError("batch_score: states of different prefix lengths")
-                cache = self.init_cache(len(states), capacity=max(s.cache.capacity for s in states))
-                cache.len = first.len
-                by_cache = {}
-                for i, s in enumerate(states):
-                    by_cache.setdefault(id(s.cache), (s.cache, [], []))
-                    by_cache[id(s.cache)][1].append(i)
-                    by_cache[id(s.cache)][2].append(s.row)
-                for c, dst, src in by_cache.values():
-                    cache.buf[:, cache._index(dst), :cache.len] = c.buf[:, c._index(src), :cache.len]
+        cache = merge_row_states(states, ys.shape[0], self.init_cache)
         logp, cache = self.forward_one_step(ys, None, xs, cache=cache)
         return logp, [RowState(cache, i) for i in range(ys.shape[0])]

@@ -4,7 +4,10 @@ no dropout / SpecAug) on the HIP kernels, then the joint CTC/attention BeamSearc
 asr/beam_search.py with the reference's weights: decoder 1 - ctc_weight, ctc ctc_weight,
 length_bonus penalty; pre-beam on the "full" scores unless ctc_weight == 1.0.
 Tokenizers: "bpe" (sentencepiece model file, as the SLURP recipes use) and "char";
-ids2tokens by the model's token_list.  LM / n-gram / transducer / streaming are out of scope.
+ids2tokens by the model's token_list.  lm= (a TransformerLM, or an ESPnetLanguageModel whose .lm is used) adds
+neural-LM shallow fusion: scorer "lm" with weight lm_weight in the same weighted sum (and so in the "full" pre-beam
+key), as the reference's Speech2Text does with lm_train_config / lm_file / lm_weight (build the LM with
+tasks/lm.build_model and load_state_dict).  Word LM / n-gram / transducer / streaming are out of scope.
 
 batch_search=True runs the reference Speech2Text's own search instead, BatchBeamSearch (top `beam` over the
 flattened hypothesis x vocabulary scores, <eos> always CTC-scored), on the cached one-step decoder: the
@@ -42,7 +45,7 @@ class Speech2Text:
     def __init__(self, asr_model, token_list: Optional[List[str]] = None, beam_size: int = 20,
                  ctc_weight: float = 0.5, penalty: float = 0.0, nbest: int = 1, maxlenratio: float = 0.0,
                  minlenratio: float = 0.0, token_type: Optional[str] = None, bpemodel: Optional[str] = None,
-                 batch_search: bool = False):
+                 batch_search: bool = False, lm=None, lm_weight: float = 1.0):
         asr_model.eval()
         self.asr_model = asr_model
         self.device = asr_model.flat.flat.device
@@ -52,6 +55,9 @@ class Speech2Text:
                        ctc=CTCPrefixScorer(asr_model.ctc, eos=asr_model.eos, blank=asr_model.blank_id),
                        length_bonus=LengthBonus())
         weights = dict(decoder=1.0 - ctc_weight, ctc=ctc_weight, length_bonus=penalty)
+        if lm is not None:
+            scorers["lm"] = getattr(lm, "lm", lm).eval()
+            weights["lm"] = lm_weight
         kw = dict(scorers=scorers, weights=weights, beam_size=beam_size, vocab_size=len(self.token_list),
                   sos=asr_model.sos, eos=asr_model.eos, token_list=self.token_list,
                   pre_beam_score_key=None if ctc_weight == 1.0 else "full")

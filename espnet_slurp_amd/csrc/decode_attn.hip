@@ -17,17 +17,26 @@
 // lanes skip both loads and carry p = 0.  All arithmetic is fp32.
 // Rows with the same src read the same K / V bytes; this version leaves that sharing to the L2 (the
 // rows arrive sorted by utterance, so the waves of one utterance run close together in time).
+//
+// esp_decode_attn_masked (the Transformer LM step) is the same kernel with a per-row key-validity byte mask
+// (N, Tk): key j of row n takes part when j < klen[n] and mask[n, j] != 0 (the reference LM hides every key
+// whose token id is 0, espnet2/lm/transformer_lm.py _target_mask).  A masked lane behaves as a lane beyond klen:
+// no load, score -inf, p = 0.  A chunk whose 64 keys are all masked while no key has been seen yet (m = -inf)
+// is skipped before exp(m - mn) could form exp(-inf - -inf); once a key has been seen m is finite and an
+// all-masked chunk rescales by exp(0) = 1.  Contract: at least one valid key per row.  With an all-ones mask
+// the arithmetic is that of the unmasked kernel, operation for operation.
 #include "common.h"
 
 namespace {
 
 constexpr int kDecodeChunk = 64;  // keys per online-softmax step: one per lane
 
-template <int DK>
+template <int DK, bool MASKED>
 __global__ void __launch_bounds__(256)
 decode_attn_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ k, long ldk, long sk,
                    const float* __restrict__ v, long ldv, long sv, float* __restrict__ out, long ldo,
-                   const int* __restrict__ src, const int* __restrict__ klen, int N, int H, float inv_sqrt_dk) {
+                   const int* __restrict__ src, const int* __restrict__ klen, int N, int H, float inv_sqrt_dk,
+                   const unsigned char* __restrict__ mask, long ldm) {
   const int lane = threadIdx.x & 63;
   const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= (long)N * H) return;  // wave-uniform
@@ -50,7 +59,8 @@ decode_attn_kernel(const float* __restrict__ q, long ldq, const float* __restric
   for (int d = 0; d < DK; ++d) acc[d] = 0.f;
   for (int j0 = 0; j0 < len; j0 += kDecodeChunk) {
     const int j = j0 + lane;
-    const bool live = j < len;
+    bool live = j < len;
+    if constexpr (MASKED) live = live && mask[(long)n * ldm + j] != 0;
     float sc = -INFINITY;
     if (live) {
       const float4* kr = reinterpret_cast<const float4*>(kp + (long)j * ldk);
@@ -65,8 +75,11 @@ decode_attn_kernel(const float* __restrict__ q, long ldq, const float* __restric
       }
       sc = dot * inv_sqrt_dk;
     }
-    // lane 0 of every chunk is live (j0 < len), so mn is finite; exp(-inf) = 0 on the first chunk
+    // unmasked: lane 0 of every chunk is live (j0 < len), so mn is finite; exp(-inf) = 0 on the first chunk
     const float mn = fmaxf(m, esp::wave_max(sc));
+    if constexpr (MASKED) {
+      if (mn == -INFINITY) continue;  // wave-uniform: nothing valid yet, l and acc are still 0
+    }
     const float a = __expf(m - mn);
     const float p = live ? __expf(sc - mn) : 0.f;
     l = l * a + p;
@@ -98,38 +111,64 @@ decode_attn_kernel(const float* __restrict__ q, long ldq, const float* __restric
 
 }  // namespace
 
+static int decode_attn_launch(const char* name, const float* q, long ldq, long qoff, const float* k, long ldk, long sk,
+                              long koff, const float* v, long ldv, long sv, long voff, float* out, long ldo, long ooff,
+                              const int* idx_host, const int* idx_dev, const unsigned char* mask, long ldm, int N, int H,
+                              int dk, int nsrc, int Tk, void* stream) {
+  ESP_ARG_CHECK(dk == 16 || dk == 32 || dk == 64, "%s: d_k %d not supported (16, 32, 64)", name, dk);
+  ESP_ARG_CHECK(N >= 1 && H >= 1 && nsrc >= 1 && Tk >= 1 && (long)N * H < (1L << 31),
+                "%s: bad sizes N=%d H=%d nsrc=%d Tk=%d", name, N, H, nsrc, Tk);
+  ESP_ARG_CHECK(q && k && v && out && idx_host && idx_dev, "%s: null argument", name);
+  const long w = (long)H * dk;
+  ESP_ARG_CHECK(qoff >= 0 && koff >= 0 && voff >= 0 && ooff >= 0 && ldq >= qoff + w && ldk >= koff + w &&
+                    ldv >= voff + w && ldo >= ooff + w,
+                "%s: a row (offset + H*d_k) does not fit its leading dimension", name);
+  ESP_ARG_CHECK(sk >= 0 && sv >= 0 && (nsrc == 1 || (sk >= (long)Tk * ldk && sv >= (long)Tk * ldv)),
+                "%s: source stride smaller than Tk rows", name);
+  ESP_ARG_CHECK(!((ldq | qoff | ldk | sk | koff | ldv | sv | voff) & 3) &&
+                    !(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15),
+                "%s: q / K / V need 16-byte aligned rows (pointers, strides and offsets %% 4 floats)", name);
+  int maxlen = 0;
+  for (int n = 0; n < N; ++n) {
+    const int s = idx_host[n], len = idx_host[N + n];
+    ESP_ARG_CHECK(s >= 0 && s < nsrc, "%s: src[%d] = %d outside [0, %d)", name, n, s, nsrc);
+    ESP_ARG_CHECK(len >= 1 && len <= Tk, "%s: klen[%d] = %d outside [1, %d]", name, n, len, Tk);
+    maxlen = len > maxlen ? len : maxlen;
+  }
+  ESP_ARG_CHECK(!mask || ldm >= maxlen, "%s: mask row pitch %ld smaller than the longest klen %d", name, ldm, maxlen);
+  const float inv = 1.0f / sqrtf((float)dk);
+  const dim3 grid((unsigned)(((long)N * H + 3) / 4)), block(256);
+  const hipStream_t st = (hipStream_t)stream;
+#define ESP_DECODE_ATTN_LAUNCH(DK, MASKED)                                                                        \
+  hipLaunchKernelGGL((decode_attn_kernel<DK, MASKED>), grid, block, 0, st, q + qoff, ldq, k + koff, ldk, sk, v + voff, \
+                     ldv, sv, out + ooff, ldo, idx_dev, idx_dev + N, N, H, inv, mask, ldm)
+  if (mask) {
+    if (dk == 16) ESP_DECODE_ATTN_LAUNCH(16, true);
+    else if (dk == 32) ESP_DECODE_ATTN_LAUNCH(32, true);
+    else ESP_DECODE_ATTN_LAUNCH(64, true);
+  } else {
+    if (dk == 16) ESP_DECODE_ATTN_LAUNCH(16, false);
+    else if (dk == 32) ESP_DECODE_ATTN_LAUNCH(32, false);
+    else ESP_DECODE_ATTN_LAUNCH(64, false);
+  }
+#undef ESP_DECODE_ATTN_LAUNCH
+  ESP_CHECK_LAUNCH(name);
+  return 0;
+}
+
 ESP_API int esp_decode_attn(const float* q, long ldq, long qoff, const float* k, long ldk, long sk, long koff,
                             const float* v, long ldv, long sv, long voff, float* out, long ldo, long ooff,
                             const int* idx_host, const int* idx_dev, int N, int H, int dk, int nsrc, int Tk,
                             void* stream) {
-  ESP_ARG_CHECK(dk == 16 || dk == 32 || dk == 64, "esp_decode_attn: d_k %d not supported (16, 32, 64)", dk);
-  ESP_ARG_CHECK(N >= 1 && H >= 1 && nsrc >= 1 && Tk >= 1 && (long)N * H < (1L << 31),
-                "esp_decode_attn: bad sizes N=%d H=%d nsrc=%d Tk=%d", N, H, nsrc, Tk);
-  ESP_ARG_CHECK(q && k && v && out && idx_host && idx_dev, "esp_decode_attn: null argument");
-  const long w = (long)H * dk;
-  ESP_ARG_CHECK(qoff >= 0 && koff >= 0 && voff >= 0 && ooff >= 0 && ldq >= qoff + w && ldk >= koff + w &&
-                    ldv >= voff + w && ldo >= ooff + w,
-                "esp_decode_attn: a row (offset + H*d_k) does not fit its leading dimension");
-  ESP_ARG_CHECK(sk >= 0 && sv >= 0 && (nsrc == 1 || (sk >= (long)Tk * ldk && sv >= (long)Tk * ldv)),
-                "esp_decode_attn: source stride smaller than Tk rows");
-  ESP_ARG_CHECK(!((ldq | qoff | ldk | sk | koff | ldv | sv | voff) & 3) &&
-                    !(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15),
-                "esp_decode_attn: q / K / V need 16-byte aligned rows (pointers, strides and offsets %% 4 floats)");
-  for (int n = 0; n < N; ++n) {
-    const int s = idx_host[n], len = idx_host[N + n];
-    ESP_ARG_CHECK(s >= 0 && s < nsrc, "esp_decode_attn: src[%d] = %d outside [0, %d)", n, s, nsrc);
-    ESP_ARG_CHECK(len >= 1 && len <= Tk, "esp_decode_attn: klen[%d] = %d outside [1, %d]", n, len, Tk);
-  }
-  const float inv = 1.0f / sqrtf((float)dk);
-  const dim3 grid((unsigned)(((long)N * H + 3) / 4)), block(256);
-  const hipStream_t st = (hipStream_t)stream;
-#define ESP_DECODE_ATTN_LAUNCH(DK)                                                                              \
-  hipLaunchKernelGGL(decode_attn_kernel<DK>, grid, block, 0, st, q + qoff, ldq, k + koff, ldk, sk, v + voff, ldv, \
-                     sv, out + ooff, ldo, idx_dev, idx_dev + N, N, H, inv)
-  if (dk == 16) ESP_DECODE_ATTN_LAUNCH(16);
-  else if (dk == 32) ESP_DECODE_ATTN_LAUNCH(32);
-  else ESP_DECODE_ATTN_LAUNCH(64);
-#undef ESP_DECODE_ATTN_LAUNCH
-  ESP_CHECK_LAUNCH("esp_decode_attn");
-  return 0;
+  return decode_attn_launch("esp_decode_attn", q, ldq, qoff, k, ldk, sk, koff, v, ldv, sv, voff, out, ldo, ooff,
+                            idx_host, idx_dev, nullptr, 0, N, H, dk, nsrc, Tk, stream);
+}
+
+ESP_API int esp_decode_attn_masked(const float* q, long ldq, long qoff, const float* k, long ldk, long sk, long koff,
+                                   const float* v, long ldv, long sv, long voff, float* out, long ldo, long ooff,
+                                   const int* idx_host, const int* idx_dev, const unsigned char* mask, long ldm, int N,
+                                   int H, int dk, int nsrc, int Tk, void* stream) {
+  ESP_ARG_CHECK(mask, "esp_decode_attn_masked: null mask");
+  return decode_attn_launch("esp_decode_attn_masked", q, ldq, qoff, k, ldk, sk, koff, v, ldv, sv, voff, out, ldo, ooff,
+                            idx_host, idx_dev, mask, ldm, N, H, dk, nsrc, Tk, stream);
 }

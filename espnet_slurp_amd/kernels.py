@@ -1482,6 +1482,88 @@ def decode_attn(q, ldq, qoff, k, ldk, sk, koff, v, ldv, sv, voff, out, ldo, ooff
                  index.host.ctypes.data, _p(index.dev), index.n, H, dk, nsrc, Tk, _st())
 
 
+def decode_attn_masked(q, ldq, qoff, k, ldk, sk, koff, v, ldv, sv, voff, out, ldo, ooff, index: DecodeIndex, mask, H,
+                       dk, nsrc, Tk):
+    """decode_attn with a per-row key-validity mask (N, >= the longest klen) uint8 on the device: key j of row n takes
+    part when j < klen[n] and mask[n, j] != 0 (esp_decode_attn_masked).  Every row needs one valid key."""
+    _f32(q, k, v, out)
+    assert index.dev.device == q.device and mask.device == q.device
+    assert mask.dtype == torch.uint8 and mask.dim() == 2 and mask.stride(1) == 1, (mask.dtype, mask.shape)
+    assert mask.shape[0] >= index.n and mask.shape[1] >= int(index.host[1].max()), (tuple(mask.shape), index.n)
+    ldm = mask.stride(0) if mask.shape[0] > 1 else mask.shape[1]
+    _native.call("esp_decode_attn_masked", _p(q), ldq, qoff, _p(k), ldk, sk, koff, _p(v), ldv, sv, voff, _p(out), ldo,
+                 ooff, index.host.ctypes.data, _p(index.dev), _p(mask), ldm, index.n, H, dk, nsrc, Tk, _st())
+
+
+# ----------------------------------------------------------------------------- Transformer LM step
+LM_STEP_FUSED = True   # the LM step's linears on esp_step_linear (5 launches per layer); False: generic kernels
+LM_STEP_MAX_ROWS = 512  # rows up to which the fused step is used (measured: DESIGN 3.6b); above: the generic kernels
+
+
+def step_linear(x, W, b, out, *, ln=None, relu=False, R=None, c0=None, cache=None, pos=0):
+    """out[n, :] = act(LN?(x[n, :]) . W^T + b) (+ R[n, :]) for a few decode rows (esp_step_linear, fp32 FMA, W
+    streamed once per 8 rows).  ln: (gamma, beta, eps) LayerNorm prologue.  c0 / cache / pos: columns [c0, M) go to
+    cache[n, pos, :] instead of out (cache (rows, positions, M - c0) fp32 with contiguous position rows, e.g. one
+    layer of a DecoderCache); out then holds columns [0, c0) (out None when c0 == 0)."""
+    N, Kin = x.shape
+    M = W.shape[0]
+    _f32(x, W, b, R, out, cache)
+    assert W.shape[1] == Kin and x.stride(1) == 1 and W.stride(1) == 1
+    c0 = M if c0 is None else c0
+    if c0 > 0:
+        assert out.shape[0] >= N and out.shape[1] >= c0 and out.stride(1) == 1, (tuple(out.shape), N, c0)
+    if R is not None:
+        assert R.shape[0] >= N and R.shape[1] >= M and R.stride(1) == 1
+    if c0 < M:
+        assert cache.dim() == 3 and cache.shape[2] == M - c0 and cache.stride(2) == 1 and cache.stride(1) == M - c0
+        rs, cap, rows = cache.stride(0), cache.shape[1], cache.shape[0]
+    else:
+        cache, rs, cap, rows = None, 0, 0, 0
+    g, be, eps = ln if ln is not None else (None, None, 0.0)
+    if g is not None:
+        assert g.numel() == Kin and be.numel() == Kin
+    _native.call("esp_step_linear", _p(x), x.stride(0), _p(W), W.stride(0), _p(b), _p(g), _p(be), float(eps), int(relu),
+                 _p(R), R.stride(0) if R is not None else 0, _p(out) if c0 > 0 else None,
+                 out.stride(0) if c0 > 0 else 0, c0, _p(cache), rs, int(pos), cap, rows, N, Kin, M, _st())
+    return out
+
+
+def lm_step_linear(x, W, b, *, ln=None, relu=False, R=None, c0=None, cache=None, pos=0):
+    """step_linear's computation for the LM step, on whichever path applies; returns the dense output, whose row n
+    holds columns [0, c0) (its row pitch may be M: read it through .stride(0)).  Fused (one esp_step_linear launch)
+    with LM_STEP_FUSED and at most LM_STEP_MAX_ROWS rows; else the generic kernels: LayerNorm, the MFMA linear_fwd
+    with its bias / ReLU / residual epilogue, and a copy of columns [c0, M) into cache[:, pos]."""
+    N, Kin = x.shape
+    M = W.shape[0]
+    c0 = M if c0 is None else c0
+    if LM_STEP_FUSED and N <= LM_STEP_MAX_ROWS:
+        out = torch.empty(N, c0, dtype=torch.float32, device=x.device) if c0 > 0 else None
+        return step_linear(x, W, b, out, ln=ln, relu=relu, R=R, c0=c0, cache=cache, pos=pos)
+    if ln is not None:
+        h, mean, rstd = torch.empty_like(x), torch.empty_like(x[:, 0]), torch.empty_like(x[:, 0])
+        layernorm_fwd(x, ln[0], ln[1], h, mean, rstd, ln[2])
+        x = h
+    out = torch.empty(N, M, dtype=torch.float32, device=x.device)
+    linear_fwd(x, W, b, out, act=ACT_RELU if relu else ACT_NONE, R=R, beta=1.0)
+    if c0 < M:
+        assert cache.shape[0] >= N and 0 <= pos < cache.shape[1] and cache.shape[2] == M - c0
+        cache[:N, pos] = out[:, c0:]
+    return out
+
+
+def step_ln_act(x, gamma, beta, eps, y, *, pe=None, xscale=1.0, L=1, pos0=0):
+    """y[r, :] = relu(LN(x[r, :])) * xscale + pe[pos0 + r % L, :] (pe None: relu(LN(x))): the LM input layer's
+    LayerNorm -> ReLU -> positional step (esp_step_ln_act).  x, y (rows, D) contiguous."""
+    rows, D = x.shape
+    _f32(x, gamma, beta, y, pe)
+    assert x.is_contiguous() and y.is_contiguous() and y.shape == x.shape
+    if pe is not None:
+        assert pe.is_contiguous() and pe.shape[1] == D
+    _native.call("esp_step_ln_act", _p(x), _p(gamma), _p(beta), float(eps), float(xscale), _p(pe), int(L), int(pos0),
+                 pe.shape[0] if pe is not None else 0, _p(y), rows, D, _st())
+    return y
+
+
 def reserve_workspace(nbytes, device):
     WS.reserve(nbytes, device)
 

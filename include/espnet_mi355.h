@@ -542,6 +542,35 @@ int esp_decode_attn(const float* q, long ldq, long qoff, const float* k, long ld
                     const float* v, long ldv, long sv, long voff, float* out, long ldo, long ooff,
                     const int* idx_host, const int* idx_dev, int N, int H, int dk, int nsrc, int Tk, void* stream);
 
+/* ---- ABI 36: the Transformer LM step (shallow fusion; espnet2/lm/transformer_lm.py batch_score over
+ * espnet/nets/pytorch_backend/transformer/encoder.py forward_one_step).
+ *
+ * esp_decode_attn_masked (csrc/decode_attn.hip): esp_decode_attn with a per-row key-validity byte mask, row n at
+ * mask + n*ldm (ldm >= the longest klen): key j of row n takes part when j < klen[n] and mask[n*ldm + j] != 0 (the LM hides the
+ * keys whose token id is 0).  Masked keys are never read.  Every row needs at least one valid key.  With an
+ * all-ones mask the result equals esp_decode_attn's bit for bit.
+ *
+ * esp_step_linear (csrc/lm_step.hip): out[n, :] = act(LN?(x[n, :]) . W^T + b) (+ R[n, :]) for N decode rows, W
+ * (M, K) row-major with pitch ldw, fp32 FMA; the weight is streamed once per tile of 8 rows.  ln_gamma / ln_beta
+ * (both or neither): LayerNorm over K with ln_eps before the product.  bias, R NULL: absent.  relu != 0: ReLU before
+ * the residual.  Columns [0, c0) are stored to out + n*ldo; columns [c0, M) to
+ * out2 + n*row_stride2 + pos*(M - c0) + (m - c0), the position-`pos` slot of row n of a (rows2, capacity2, M - c0)
+ * buffer with row pitch row_stride2 (a DecoderCache layer: K | V written in place).  c0 = M: no split (out2 may be
+ * NULL).  The split store is checked on the host (0 <= pos < capacity2, N <= rows2, row_stride2 >= capacity2*(M-c0):
+ * status -1).  K a multiple of 4, at most 2048; x / W rows 16-byte aligned.  R may be `out`.
+ *
+ * esp_step_ln_act (csrc/lm_step.hip): y[r, :] = relu(LN(x[r, :])) * xscale + pe[pos0 + r % L, :] for `rows`
+ * contiguous rows of D floats (pe NULL: y = relu(LN(x)), the identity positional step); pe has pe_rows rows. */
+int esp_decode_attn_masked(const float* q, long ldq, long qoff, const float* k, long ldk, long sk, long koff,
+                           const float* v, long ldv, long sv, long voff, float* out, long ldo, long ooff,
+                           const int* idx_host, const int* idx_dev, const unsigned char* mask, long ldm, int N, int H,
+                           int dk, int nsrc, int Tk, void* stream);
+int esp_step_linear(const float* x, long ldx, const float* W, long ldw, const float* bias, const float* ln_gamma,
+                    const float* ln_beta, float ln_eps, int relu, const float* R, long ldr, float* out, long ldo, int c0,
+                    float* out2, long row_stride2, int pos, int capacity2, int rows2, int N, int K, int M, void* stream);
+int esp_step_ln_act(const float* x, const float* gamma, const float* beta, float eps, float xscale, const float* pe,
+                    int L, int pos0, int pe_rows, float* y, int rows, int D, void* stream);
+
 /* ---- workspace sizes.  Every launcher that takes a scratch `work` buffer also takes its size
  * in bytes and fails (status -1, esp_last_error) when it is smaller than the size below, which is
  * computed by the same code that picks the launcher's chunking: callers size their buffers from
