@@ -85,7 +85,6 @@ SIGNATURES = {
     "esp_attn_softmax_fwd": [P, P, I, I, F, P, I, I, P, P, F, U64, I, I, I, L, L, P, P],
     "esp_attn_softmax_bwd": [P, P, P, F, U64, F, L, I, L, P],
     "esp_relshift_bwd": [P, L, P, L, I, I, I, I, P],
-    "esp_relpos_softmax_fwd": [P, P, L, I, I, P, F, P, P, P, F, U64, I, L, P],
     "esp_relpos_attn_fwd": [P, P, P, L, P, L, I, I, F, P, P, P, F, U64, I, L, P],
     "esp_relpos_attn_probs": [P, P, P, L, P, L, I, I, I, F, P, P, P, F, U64, I, L, P, P],
     "esp_attn_bwd_prep": [P, L, P, L, I, I, I, I, P, P, L, I, P],
@@ -142,7 +141,7 @@ _RESTYPES = {"esp_last_error": ctypes.c_char_p, "esp_abi_version": I, "esp_attn_
              "esp_get_gemm_compute": I, "esp_set_splitk_mode": I,
              "esp_f32_gemm_products": I}
 _RESTYPES.update({k: L for k in SIGNATURES if k.endswith("_workspace_bytes")})
-ABI_VERSION = 36  # bumped whenever a signature in include/espnet_mi355.h changes
+ABI_VERSION = 37  # bumped whenever a signature in include/espnet_mi355.h changes
 
 _lib = None
 

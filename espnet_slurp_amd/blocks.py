@@ -217,116 +217,134 @@ class RelPositionMultiHeadedAttention(nn.Module):
         pa = self.p if training else 0.0
         sa = seeds.next()
         tv = tvalid if self.legacy else None
-        # a legacy length-bucketed batch (rel_shift at T' = *tvalid) takes the materialised kernels, which read
-        # T' on device; the opt-in flash / score-gradient forms stay for every other batch
-        if K.flash_ok(T, dk) and tv is None:
+        # the one place the kernels are chosen (kernels.relpos_attn_paths); bwd dispatches on c.bwd
+        fwd, bwd, ctx_fp32 = K.relpos_attn_paths(T, dk, self.legacy, tv is not None)
+        c = Ctx(x=x2d, qkv=qkv, p=p, pos=pos_emb, q_u=q_u, q_v=q_v, flash=fwd == "flash", bwd=bwd,
+                bwd_ds=bwd == "ds", pa=pa, sa=sa, B=B, T=T, P=P, tvalid=tv)
+        if fwd == "flash":
             # scores, softmax, dropout and P.V in one kernel: only ctx and 2 floats per row to HBM
             ctx_ = empty(M, D, like=x2d)
-            stats = empty(Z * T * 2, like=x2d)
+            c.klen = klen  # (the flash backward recomputes the masked scores)
+            c.stats = empty(Z * T * 2, like=x2d)
             K.relpos_flash_fwd(q_u, q_v, qkv, 3 * D, qkv, 3 * D, p, D, relpos, B, H, math.sqrt(dk), klen, ctx_, D,
-                               stats, pa, sa, T, k_off=D, v_off=2 * D)
-            if out is None:
-                out = empty(M, D, like=x2d)
-            pr = p_res if training else 0.0
-            so = seeds.next()
-            self.linear_out.fwd(ctx_, out, drop_p=pr, seed=so, R=resid, beta=1.0, out_off=out_off, ldo=ldo)
-            return out, Ctx(x=x2d, qkv=qkv, p=p, pos=pos_emb, q_u=q_u, q_v=q_v, ctx=ctx_, stats=stats, klen=klen,
-                            flash=True, pa=pa, sa=sa, pr=pr, so=so, B=B, T=T, P=P)
-        Tp, Pp = K.pitch(T), K.pitch(P)  # 16-B aligned score rows
-        ac = empty(Z * T * Tp, like=x2d)
-        pdrop = empty(Z * T * Tp, like=x2d) if pa > 0 else None
-        if K.relpos_probs_ok(T, dk) and not K.ATTN_FWD32:
-            # ac and the bd band on the MFMA inside the softmax kernel (latest and legacy
-            # rel_shift): only attn and its dropout copy reach HBM
-            K.relpos_attn_probs(q_u, q_v, qkv, 3 * D, p, D, relpos, B, H, math.sqrt(dk), klen, ac, pdrop, pa, sa, T,
-                                Tp, k_off=D, tvalid=tv)
-        elif not self.legacy and K.relpos_fused_ok(T, dk):
-            K.relpos_attn_fwd(q_u, q_v, qkv, 3 * D, p, D, B, H, math.sqrt(dk), klen, ac, pdrop, pa, sa, T, Tp,
-                              k_off=D)
+                               c.stats, pa, sa, T, k_off=D, v_off=2 * D)
         else:
-            # ac[z] = q_u[z] k[b,h]^T
-            K.gemm(T, T, dk, q_u, qkv, ac, mode_a=K.KC, lda=dk, mode_b=K.KC, ldb=3 * D, ldc=Tp, b_off=D,
-                   batch=Z, nb2=B, sa=(B * T * dk, T * dk), sb=(dk, T * 3 * D), sc=(B * T * Tp, T * Tp))
-            bd = empty(Z * T * Pp, like=x2d)
-            K.gemm(T, P, dk, q_v, p, bd, mode_a=K.KC, lda=dk, mode_b=K.KC, ldb=D, ldc=Pp,
-                   batch=Z, nb2=B, sa=(B * T * dk, T * dk), sb=(dk, 0), sc=(B * T * Pp, T * Pp))
-            K.attn_softmax_fwd(ac, bd, relpos, P, math.sqrt(dk), klen, B, False, ac, pdrop, pa, sa, Z, T, T,
-                               lds=Tp, ldp=Pp, tvalid=tv)
-            del bd
-        attn = ac
-        pv = pdrop if pdrop is not None else attn
-        # the dS-only backward (kernels.RELPOS_BWD_DS): latest rel_shift, fp32 compute, no other opt-in form
-        bwd_ds = (not self.legacy and K.RELPOS_BWD_DS and K.relpos_bwd_ds_ok(T, dk) and not K.FUSED_ATTN_BWD
-                  and not K.ATTN_DSCORES and K._COMPUTE[0] == K.GEMM_FP32)
-        # ctx feeds only linear_out (forward and weight gradient): planes from the P.V epilogue (the
-        # score-gradient epilogue, ESP_ATTN_DSCORES and the dS-only backward, reads it in fp32)
-        npl = K.planes_mode() if D % 8 == 0 and not K.ATTN_DSCORES and not bwd_ds else 0
-        ctx_ = K.Planes(M, D, x2d.device, npl) if npl else empty(M, D, like=x2d)
-        K.gemm(T, dk, T, pv, qkv, ctx_, mode_a=K.KC, lda=Tp, mode_b=K.RC, ldb=3 * D, ldc=D, b_off=2 * D,
-               batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(dk, T * 3 * D), sc=(dk, T * D))
+            Tp, Pp = K.pitch(T), K.pitch(P)  # 16-B aligned score rows
+            attn = empty(Z * T * Tp, like=x2d)
+            pdrop = empty(Z * T * Tp, like=x2d) if pa > 0 else None
+            if fwd == "probs":
+                # ac and the bd band on the MFMA inside the softmax kernel (latest and legacy
+                # rel_shift): only attn and its dropout copy reach HBM
+                K.relpos_attn_probs(q_u, q_v, qkv, 3 * D, p, D, relpos, B, H, math.sqrt(dk), klen, attn, pdrop, pa, sa,
+                                    T, Tp, k_off=D, tvalid=tv)
+            elif fwd == "block32":
+                K.relpos_attn_fwd(q_u, q_v, qkv, 3 * D, p, D, B, H, math.sqrt(dk), klen, attn, pdrop, pa, sa, T, Tp,
+                                  k_off=D)
+            else:
+                # ac[z] = q_u[z] k[b,h]^T (softmaxed in place)
+                K.gemm(T, T, dk, q_u, qkv, attn, mode_a=K.KC, lda=dk, mode_b=K.KC, ldb=3 * D, ldc=Tp, b_off=D,
+                       batch=Z, nb2=B, sa=(B * T * dk, T * dk), sb=(dk, T * 3 * D), sc=(B * T * Tp, T * Tp))
+                bd = empty(Z * T * Pp, like=x2d)
+                K.gemm(T, P, dk, q_v, p, bd, mode_a=K.KC, lda=dk, mode_b=K.KC, ldb=D, ldc=Pp,
+                       batch=Z, nb2=B, sa=(B * T * dk, T * dk), sb=(dk, 0), sc=(B * T * Pp, T * Pp))
+                K.attn_softmax_fwd(attn, bd, relpos, P, math.sqrt(dk), klen, B, False, attn, pdrop, pa, sa, Z, T, T,
+                                   lds=Tp, ldp=Pp, tvalid=tv)
+                del bd
+            c.attn = attn
+            c.pv = pdrop if pdrop is not None else attn
+            # ctx feeds only linear_out (forward and weight gradient): planes from the P.V epilogue, unless the
+            # backward's score-gradient epilogue reads it in fp32
+            npl = K.planes_mode() if D % 8 == 0 and not ctx_fp32 else 0
+            ctx_ = K.Planes(M, D, x2d.device, npl) if npl else empty(M, D, like=x2d)
+            K.gemm(T, dk, T, c.pv, qkv, ctx_, mode_a=K.KC, lda=Tp, mode_b=K.RC, ldb=3 * D, ldc=D, b_off=2 * D,
+                   batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(dk, T * 3 * D), sc=(dk, T * D))
+        c.ctx = ctx_
         if out is None:
             out = empty(M, D, like=x2d)
-        pr = p_res if training else 0.0
-        so = seeds.next()
-        self.linear_out.fwd(ctx_, out, drop_p=pr, seed=so, R=resid, beta=1.0, out_off=out_off, ldo=ldo)
-        return out, Ctx(x=x2d, qkv=qkv, p=p, pos=pos_emb, q_u=q_u, q_v=q_v, attn=attn, pv=pv, ctx=ctx_,
-                        flash=False, pa=pa, sa=sa, pr=pr, so=so, B=B, T=T, P=P, tvalid=tv, bwd_ds=bwd_ds)
+        c.pr = p_res if training else 0.0
+        c.so = seeds.next()
+        self.linear_out.fwd(ctx_, out, drop_p=c.pr, seed=c.so, R=resid, beta=1.0, out_off=out_off, ldo=ldo)
+        return out, c
 
     def bwd(self, c, dout):
+        H, dk = self.h, self.d_k
+        D = H * dk
+        dz = grad_buf(dout)
+        K.scale_dropout(dout, dz, drop_p=c.pr, seed=c.so)
+        dctx = self.linear_out.bwd(dz, c.ctx)
+        dqkv = empty(c.B * c.T, 3 * D, like=dout)
+        if c.bwd == "flash":
+            dp = self._bwd_flash(c, dctx, dqkv)
+        elif c.bwd == "ds":
+            dp = self._bwd_ds(c, dctx, dqkv)
+        else:
+            dp = self._bwd_dbd(c, dctx, dqkv)
+        # linear_pos weight grad only (pos_emb is a constant table)
+        K.gemm(D, D, c.P, dp, c.pos, self.linear_pos.weight.grad, mode_a=K.RC, lda=D, mode_b=K.RC, ldb=D, ldc=D,
+               R=self.linear_pos.weight.grad, beta=1.0)
+        w, _ = self._wqkv()
+        gw, gb = self._wqkv(grad=True)
+        K.linear_bwd_weight(dqkv, c.x, gw, gb)
+        dx = empty(c.B * c.T, D, like=dout)
+        K.linear_bwd_data(dqkv, w, dx)
+        return dx
+
+    def _dv(self, c, pv, dctx, dqkv):
+        """dV = pv^T dctx -> dqkv[:, 2D:3D]"""
+        dk, B, T, Tp = self.d_k, c.B, c.T, K.pitch(c.T)
+        D = self.h * dk
+        K.gemm(T, dk, T, pv, dctx, dqkv, mode_a=K.RC, lda=Tp, mode_b=K.RC, ldb=D, ldc=3 * D, c_off=2 * D,
+               batch=self.h * B, nb2=B, sa=(B * T * Tp, T * Tp), sb=(dk, T * D), sc=(dk, T * 3 * D))
+
+    def _dk(self, c, dS, dqkv):
+        """dk = dS^T q_u -> dqkv[:, D:2D]"""
+        dk, B, T, Tp = self.d_k, c.B, c.T, K.pitch(c.T)
+        D = self.h * dk
+        K.gemm(T, dk, T, dS, c.q_u, dqkv, mode_a=K.RC, lda=Tp, mode_b=K.RC, ldb=dk, ldc=3 * D, c_off=D,
+               batch=self.h * B, nb2=B, sa=(B * T * Tp, T * Tp), sb=(B * T * dk, T * dk), sc=(dk, T * 3 * D))
+
+    def _bwd_dbd(self, c, dctx, dqkv):
+        """The backward forms that materialise the rel_shift adjoint dbd (c.bwd "rowpass", "fused", "dscores"):
+        fills dqkv, accumulates the pos_bias gradients, returns dp (the linear_pos gradient input)."""
         H, dk = self.h, self.d_k
         D = H * dk
         B, T, P = c.B, c.T, c.P
         M, Z = B * T, H * B
         relpos = 2 if self.legacy else 1
-        dz = grad_buf(dout)
-        K.scale_dropout(dout, dz, drop_p=c.pr, seed=c.so)
-        dctx = self.linear_out.bwd(dz, c.ctx)
-        dqkv = empty(M, 3 * D, like=dout)
-        if c.flash:
-            return self._bwd_flash(c, dctx, dqkv)
-        if c.bwd_ds:
-            return self._bwd_ds(c, dctx, dqkv)
         Tp, Pp = K.pitch(T), K.pitch(P)
-        dS = empty(Z * T * Tp, like=dout)
-        # the fused dP + softmax/rel_shift adjoint kernel measures slower than the K=64 GEMM + the
-        # row-wise adjoint pass at C2 (198 vs 157 us per layer): opt-in until it is reworked
-        fused = not self.legacy and K.relpos_fused_ok(T, dk) and K.FUSED_ATTN_BWD
-        dscores = not fused and K.ATTN_DSCORES and c.tvalid is None  # (legacy + length bucket: the row-wise pass)
-        # latest rel_shift, row-wise adjoint: dbd in the kept zeroed buffer, only its band written
-        band = None if (self.legacy or fused or dscores or Tp % 4 or T > 1024) else K.relpos_band_buffer(Z, T, Pp, dout.device)
-        dbd = band if band is not None else empty(Z * T * Pp, like=dout)
-        if dscores:
+        dS = empty(Z * T * Tp, like=dctx)
+        # latest rel_shift, row-wise adjoint: dbd in the kept zeroed buffer, only its band written (the buffer is
+        # stateful, so this one choice is made here and not in kernels.relpos_attn_paths)
+        band = None
+        if c.bwd == "rowpass" and not self.legacy and Tp % 4 == 0 and T <= 1024:
+            band = K.relpos_band_buffer(Z, T, Pp, dctx.device)
+        dbd = band if band is not None else empty(Z * T * Pp, like=dctx)
+        if c.bwd == "dscores":
             # dS = P (drop'(dP) - dot) / sqrt(dk) and its rel_shift adjoint in the dP GEMM's epilogue,
             # dot_i = dctx_i . ctx_i (= sum_j P_drop dP): no dP tensor, no row-wise pass
-            dot = empty(Z * T, like=dout)
+            dot = empty(Z * T, like=dctx)
             K.attn_bwd_prep(dctx, D, c.ctx, D, B, H, dk, T, dot, dbd, Pp, relpos)
             K.attn_dscores(dctx, D, c.qkv, 3 * D, c.attn, dot, dS, dbd, Pp, relpos, B, H, dk, math.sqrt(dk), c.pa,
                            c.sa, T, Tp, v_off=2 * D)
-        elif fused:  # dP = dctx v^T on the MFMA inside the softmax / rel_shift adjoint kernel
+        elif c.bwd == "fused":  # dP = dctx v^T on the MFMA inside the softmax / rel_shift adjoint kernel
             K.relpos_attn_bwd(dctx, D, c.qkv, 3 * D, c.attn, dS, dbd, Pp, B, H, math.sqrt(dk), c.pa, c.sa, T, Tp,
                               v_off=2 * D)
         else:  # dP = dctx v^T  (into a (Z,T,T) buffer)
             K.gemm(T, T, dk, dctx, c.qkv, dS, mode_a=K.KC, lda=D, mode_b=K.KC, ldb=3 * D, ldc=Tp, b_off=2 * D,
                    batch=Z, nb2=B, sa=(dk, T * D), sb=(dk, T * 3 * D), sc=(B * T * Tp, T * Tp))
-        # dV = pv^T dctx -> dqkv[:, 2D:3D]
-        K.gemm(T, dk, T, c.pv, dctx, dqkv, mode_a=K.RC, lda=Tp, mode_b=K.RC, ldb=D, ldc=3 * D, c_off=2 * D,
-               batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(dk, T * D), sc=(dk, T * 3 * D))
-        if fused or dscores:
-            pass
-        elif band is not None:
+        self._dv(c, c.pv, dctx, dqkv)
+        if c.bwd == "rowpass" and band is not None:
             K.attn_softmax_bwd_relpos_band(c.attn, dS, dS, dbd, Pp, c.pa, c.sa, math.sqrt(dk), Z * T, T, Tp)
-        else:  # softmax + rel_shift adjoints in one pass (latest and legacy)
+        elif c.bwd == "rowpass":  # softmax + rel_shift adjoints in one pass (latest and legacy)
             K.attn_softmax_bwd_relpos(c.attn, dS, dS, dbd, Pp, c.pa, c.sa, math.sqrt(dk), Z * T, T, Tp, relpos=relpos,
                                       tvalid=c.tvalid)
         # dq_u = dS k -> dqkv[:, 0:D]
         K.gemm(T, dk, T, dS, c.qkv, dqkv, mode_a=K.KC, lda=Tp, mode_b=K.RC, ldb=3 * D, ldc=3 * D, b_off=D,
                batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(dk, T * 3 * D), sc=(dk, T * 3 * D))
-        # dk = dS^T q_u -> dqkv[:, D:2D]
-        K.gemm(T, dk, T, dS, c.q_u, dqkv, mode_a=K.RC, lda=Tp, mode_b=K.RC, ldb=dk, ldc=3 * D, c_off=D,
-               batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(B * T * dk, T * dk), sc=(dk, T * 3 * D))
+        self._dk(c, dS, dqkv)
         K.colsum(dqkv, self.pos_bias_u.grad.view(-1), accumulate=True, M=M, N=D, ld=3 * D)
         # dq_v = dbd p -> tmp
-        tmp = empty(M, D, like=dout)
+        tmp = empty(M, D, like=dctx)
         if not self.legacy and dk == 64:  # the band of each row tile only (dbd is 0 outside it)
             K.relpos_dqv(dbd, Pp, c.p, D, tmp, D, B, H, T)
         else:
@@ -335,29 +353,20 @@ class RelPositionMultiHeadedAttention(nn.Module):
         K.colsum(tmp, self.pos_bias_v.grad.view(-1), accumulate=True)
         K.add2d(tmp, D, dqkv, 3 * D, M, D)
         # dp[:, h] = sum_b dbd[h,b]^T q_v[h,b]   (K = B*T)
-        dp = empty(P, D, like=dout)
+        dp = empty(P, D, like=dctx)
         K.gemm(P, dk, B * T, dbd, c.q_v, dp, mode_a=K.RC, lda=Pp, mode_b=K.RC, ldb=dk, ldc=D,
                batch=H, nb2=1, sa=(B * T * Pp, 0), sb=(B * T * dk, 0), sc=(dk, 0))
-        # linear_pos weight grad only (pos_emb is a constant table)
-        K.gemm(D, D, P, dp, c.pos, self.linear_pos.weight.grad, mode_a=K.RC, lda=D, mode_b=K.RC, ldb=D, ldc=D,
-               R=self.linear_pos.weight.grad, beta=1.0)
-        w, _ = self._wqkv()
-        gw, gb = self._wqkv(grad=True)
-        K.linear_bwd_weight(dqkv, c.x, gw, gb)
-        dx = empty(M, D, like=dout)
-        K.linear_bwd_data(dqkv, w, dx)
-        return dx
-
+        return dp
 
     def _bwd_ds(self, c, dctx, dqkv):
         """Latest rel_shift backward that reads dS directly (kernels.RELPOS_BWD_DS): the rel_shift adjoint dbd is
         dS re-indexed, so neither dP nor dbd nor a separate dq_v is formed.  prep (row dots) -> dS from the dP
         GEMM's epilogue -> dV -> dq = dS k + Dbd p and the pos_bias partials in one kernel -> dk -> dp along
-        dS's diagonals (+ the pos_bias reduction) -> linear_pos weight gradient."""
+        dS's diagonals (+ the pos_bias reduction); returns dp."""
         H, dk = self.h, self.d_k
         D = H * dk
         B, T, P = c.B, c.T, c.P
-        M, Z = B * T, H * B
+        Z = H * B
         Tp = K.pitch(T)
         dS = empty(Z * T * Tp, like=dctx)
         # dS = P (drop'(dP) - dot) / sqrt(dk), dot_i = dctx_i . ctx_i (= sum_j P_drop dP)
@@ -365,37 +374,25 @@ class RelPositionMultiHeadedAttention(nn.Module):
         K.attn_bwd_prep(dctx, D, c.ctx, D, B, H, dk, T, dot, None, 0, 1)
         K.attn_dscores(dctx, D, c.qkv, 3 * D, c.attn, dot, dS, None, 0, 1, B, H, dk, math.sqrt(dk), c.pa, c.sa, T,
                        Tp, v_off=2 * D)
-        # dV = pv^T dctx -> dqkv[:, 2D:3D]
-        K.gemm(T, dk, T, c.pv, dctx, dqkv, mode_a=K.RC, lda=Tp, mode_b=K.RC, ldb=D, ldc=3 * D, c_off=2 * D,
-               batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(dk, T * D), sc=(dk, T * 3 * D))
+        self._dv(c, c.pv, dctx, dqkv)
         # dq = dq_u + dq_v -> dqkv[:, 0:D]; per-block column sums of each for the pos_bias gradients
         bias_part = empty(Z * ((T + 31) // 32) * 2 * dk, like=dctx)
         K.relpos_dq(dS, Tp, c.qkv, 3 * D, c.p, D, dqkv, 3 * D, bias_part, B, H, T, k_off=D)
-        # dk = dS^T q_u -> dqkv[:, D:2D]
-        K.gemm(T, dk, T, dS, c.q_u, dqkv, mode_a=K.RC, lda=Tp, mode_b=K.RC, ldb=dk, ldc=3 * D, c_off=D,
-               batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(B * T * dk, T * dk), sc=(dk, T * 3 * D))
+        self._dk(c, dS, dqkv)
         # dp[:, h] = sum_b Dbd[h,b]^T q_v[h,b]; pos_bias_u / pos_bias_v grads += the partials, in fixed order
         dp = empty(P, D, like=dctx)
         K.relpos_dp(dS, Tp, c.q_v, 1, B, H, T, dp, D, bias_part, None, self.pos_bias_u.grad.view(-1),
                     self.pos_bias_v.grad.view(-1), dqkv, 3 * D)
-        del dS
-        K.gemm(D, D, P, dp, c.pos, self.linear_pos.weight.grad, mode_a=K.RC, lda=D, mode_b=K.RC, ldb=D, ldc=D,
-               R=self.linear_pos.weight.grad, beta=1.0)
-        w, _ = self._wqkv()
-        gw, gb = self._wqkv(grad=True)
-        K.linear_bwd_weight(dqkv, c.x, gw, gb)
-        dx = empty(M, D, like=dctx)
-        K.linear_bwd_data(dqkv, w, dx)
-        return dx
+        return dp
 
     def _bwd_flash(self, c, dctx, dqkv):
         """Flash backward: scores recomputed per (z, 32 rows); dq (q_u and q_v paths) and the
         pos_bias partials in-kernel; dK / dV as batched GEMMs over the dS / P_drop it writes;
-        linear_pos gradient from dS along its diagonals (no dbd tensor)."""
+        linear_pos gradient input dp from dS along its diagonals (no dbd tensor); returns dp."""
         H, dk = self.h, self.d_k
         D = H * dk
         B, T, P = c.B, c.T, c.P
-        M, Z = B * T, H * B
+        Z = H * B
         rel = 2 if self.legacy else 1
         Tp = K.pitch(T)
         nqb = (T + 31) // 32
@@ -406,23 +403,12 @@ class RelPositionMultiHeadedAttention(nn.Module):
         K.relpos_flash_bwd(c.q_u, c.q_v, c.qkv, 3 * D, c.qkv, 3 * D, c.p, D, rel, B, H, math.sqrt(dk), c.klen, c.ctx,
                            dctx, D, c.stats, c.pa, c.sa, T, dqkv, 3 * D, dS, pd, Tp, bias_part, carry,
                            k_off=D, v_off=2 * D)
-        # dV = P_drop^T dctx -> dqkv[:, 2D:3D];  dK = dS^T q_u -> dqkv[:, D:2D]
-        K.gemm(T, dk, T, pd, dctx, dqkv, mode_a=K.RC, lda=Tp, mode_b=K.RC, ldb=D, ldc=3 * D, c_off=2 * D,
-               batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(dk, T * D), sc=(dk, T * 3 * D))
-        K.gemm(T, dk, T, dS, c.q_u, dqkv, mode_a=K.RC, lda=Tp, mode_b=K.RC, ldb=dk, ldc=3 * D, c_off=D,
-               batch=Z, nb2=B, sa=(B * T * Tp, T * Tp), sb=(B * T * dk, T * dk), sc=(dk, T * 3 * D))
+        self._dv(c, pd, dctx, dqkv)
+        self._dk(c, dS, dqkv)
         dp = empty(P, D, like=dctx)
         K.relpos_dp(dS, Tp, c.q_v, rel, B, H, T, dp, D, bias_part, carry, self.pos_bias_u.grad.view(-1),
                     self.pos_bias_v.grad.view(-1), dqkv, 3 * D)
-        del dS, pd
-        K.gemm(D, D, P, dp, c.pos, self.linear_pos.weight.grad, mode_a=K.RC, lda=D, mode_b=K.RC, ldb=D, ldc=D,
-               R=self.linear_pos.weight.grad, beta=1.0)
-        w, _ = self._wqkv()
-        gw, gb = self._wqkv(grad=True)
-        K.linear_bwd_weight(dqkv, c.x, gw, gb)
-        dx = empty(M, D, like=dctx)
-        K.linear_bwd_data(dqkv, w, dx)
-        return dx
+        return dp
 
 
 class MultiHeadedAttention(nn.Module):

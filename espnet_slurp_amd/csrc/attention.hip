@@ -606,112 +606,13 @@ __global__ void relshift_bwd_kernel(const float* __restrict__ dS, long lds, floa
   }
 }
 
-// ---------------------------------------------------------------- fused latest rel-pos softmax
-// One block per (32 query rows, z): the bd window of the block is computed on the MFMA
-//   Sbd[r][c] = q_v[z][i0 + r] . p[kmin + c],   kmin = T - 32 - i0,  c in [0, T + 31)
-// (the 32 x (T+31) band of (q+v) p^T that rel_shift reads: bd_shift[i][j] = Sbd[i-i0][j-(i-i0)+31])
-// into LDS, then each wave finishes 8 score rows: s = (ac + bd_shift) / sqrt(dk), key mask,
-// softmax (wave shuffles), attention-dropout copy.  Replaces the (Z,T,2T-1) bd GEMM + its HBM
-// round trip + the separate softmax pass.  d_k = 64; LDS = 32 x WP floats (WP = 32*ceil((T+31)/32)+4).
-// MFMA operand k-order: lane half hf supplies d = 32c + 16hf + s at step (c, s) for both operands.
-template <int PER>
-__global__ __launch_bounds__(256) void relpos_softmax_fwd_kernel(
-    const float* __restrict__ qv, const float* __restrict__ pm, long ldpm, int nb, int H, const float* ac,
-    float sqrt_dk, const int* __restrict__ klen, float* attn, float* __restrict__ pdrop, uint32_t thr, float dscale,
-    uint64_t seed, int T, long lds, int WP, const uint64_t* __restrict__ key) {
-  extern __shared__ __attribute__((aligned(16))) float sbd[];  // [32][WP]
-  seed = esp::keyed(seed, key);
-  const int z = blockIdx.y;
-  const int i0 = blockIdx.x * RP_ROWS;
-  const int head = z / nb, b = z - head * nb;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int hf = lane >> 5, l32 = lane & 31;
-  const int P = 2 * T - 1;
-  const int kmin = T - RP_ROWS - i0;
-  const int ntile = (T + RP_ROWS - 1 + 31) / 32;
-
-  // A fragments: row i0 + l32 of q_v[z] (rows past T clamped: their scores are never used)
-  float af[2][16];
-  {
-    const float* q = qv + ((long)z * T + min(i0 + l32, T - 1)) * RP_DK;
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float4 v = *reinterpret_cast<const float4*>(q + 32 * c + 16 * hf + 4 * u);
-        af[c][4 * u] = v.x; af[c][4 * u + 1] = v.y; af[c][4 * u + 2] = v.z; af[c][4 * u + 3] = v.w;
-      }
-  }
-  for (int ct = wave; ct < ntile; ct += 4) {
-    const int k = min(max(kmin + ct * 32 + l32, 0), P - 1);
-    const float* pr = pm + (long)k * ldpm + head * RP_DK;
-    float bfr[2][16];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float4 v = *reinterpret_cast<const float4*>(pr + 32 * c + 16 * hf + 4 * u);
-        bfr[c][4 * u] = v.x; bfr[c][4 * u + 1] = v.y; bfr[c][4 * u + 2] = v.z; bfr[c][4 * u + 3] = v.w;
-      }
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int st = 0; st < 16; ++st) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[c][st], bfr[c][st], acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sbd[((r & 3) + 8 * (r >> 2) + 4 * hf) * WP + ct * 32 + l32] = acc[r];
-  }
-  __syncthreads();
-
-  const int* klp = klen;
-  int kl = klp ? klp[b] : T;
-  if (kl > T) kl = T;
-  for (int rr = wave; rr < RP_ROWS; rr += 4) {
-    const int i = i0 + rr;
-    if (i >= T) break;
-    const long row = (long)z * T + i;
-    const float* acr = ac + row * lds;
-    const float* sb = sbd + rr * WP + (RP_ROWS - 1 - rr);
-    float v[PER];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int e = 0; e < PER; ++e) {
-      const int j = lane + 64 * e;
-      float sc = -INFINITY;
-      if (j < T && j < kl) sc = (acr[j] + sb[j]) / sqrt_dk;
-      v[e] = sc;
-      mx = fmaxf(mx, sc);
-    }
-    mx = esp::wave_max(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int e = 0; e < PER; ++e) {
-      const float pe = v[e] == -INFINITY ? 0.f : expf(v[e] - mx);
-      v[e] = pe;
-      sum += pe;
-    }
-    sum = esp::wave_sum(sum);
-    const float inv = sum > 0.f ? 1.0f / sum : 0.f;
-    float* ar = attn + row * lds;
-    float* pd = pdrop ? pdrop + row * lds : nullptr;
-#pragma unroll
-    for (int e = 0; e < PER; ++e) {
-      const int j = lane + 64 * e;
-      if (j < T) {
-        const float pe = v[e] * inv;
-        ar[j] = pe;
-        if (pd) pd[j] = esp::keep_elem(seed, (uint64_t)(row * T + j), thr) ? pe * dscale : 0.f;
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------- fused latest rel-pos attention scores
 // The whole score path of one (32 query rows, z) block in one kernel — no (Z,T,T) ac and no
 // (Z,T,2T-1) bd tensor in HBM:
-//   1. bd band window  Sbd[r][c] = q_v[i0+r] . p[kmin+c]     (MFMA, LDS)          as above
+//   1. bd band window  Sbd[r][c] = q_v[i0+r] . p[kmin+c],  kmin = T - 32 - i0,  c in [0, T + 31): the
+//      32 x (T+31) band of (q+v) p^T that rel_shift reads, bd_shift[i][j] = Sbd[i-i0][j-(i-i0)+31]
+//      (MFMA into LDS: 32 x WP floats, WP = 32*ceil((T+31)/32)+4; operand k-order: lane half hf
+//      supplies d = 32c + 16hf + s at step (c, s) for both operands)
 //   2. ac tiles        ac[r][j]  = q_u[i0+r] . k[j]          (MFMA, registers; wave w owns
 //                                                            key tiles w, w+4, ...)
 //   3. s = (ac + Sbd[r][j-r+31]) / sqrt(dk), key mask, row max / sum by xor-shuffles inside the
@@ -930,6 +831,24 @@ constexpr int RW_ROWS = 16, RW_PITCH = 37;
 // two rows, bank (a/4) mod 64) is conflict-free, with the column XOR-ed by 16 in rows 4..7 and 12..15
 // so the two row groups of a ds_write_b32 half land 16 banks apart too (68: the reads conflicted 2-way)
 constexpr int RW_SPITCH = 64;
+// the dropout draws of columns ix .. ix + 3 of one score row (ix % 4 == 0), for the two probabilities kernels'
+// store tails: two hash pairs when row * T is even -- on 32-bit index arithmetic when every index of the launch
+// is below 2^32 (the same masks) -- else four element draws
+__device__ __forceinline__ void keep_quad(uint64_t seed, uint64_t ix, uint32_t thr, bool even_T, bool idx32, bool& k0,
+                                          bool& k1, bool& k2, bool& k3) {
+  if (even_T && idx32) {
+    esp::keep_pair32(seed, (uint32_t)ix, thr, k0, k1);
+    esp::keep_pair32(seed, (uint32_t)ix + 2, thr, k2, k3);
+  } else if (even_T) {
+    esp::keep_pair(seed, ix, thr, k0, k1);
+    esp::keep_pair(seed, ix + 2, thr, k2, k3);
+  } else {
+    k0 = esp::keep_elem(seed, ix, thr);
+    k1 = esp::keep_elem(seed, ix + 1, thr);
+    k2 = esp::keep_elem(seed, ix + 2, thr);
+    k3 = esp::keep_elem(seed, ix + 3, thr);
+  }
+}
 // SPLIT = 2 (the bf16 mode's legacy rel_shift past 16 key tiles): a row group's keys are shared by
 // two waves of the block (tiles [0, NTA) and [NTA, 2 NTA)), half the score registers each; the row
 // max and sum are combined through LDS with one block barrier each.  (As an fp32 option it measured
@@ -1087,6 +1006,7 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_fwd16_kernel(
     }
   }
 
+  // (this softmax and the store tail below have a second copy at the end of relpos_probs_lds_kernel: change both)
   // softmax over each row: a row's keys sit in the 16 lanes of one quarter x NTA tiles
   float nm[4], inv[4];  // -max * log2(e) (P2) or -max, and 1 / sum
 #pragma unroll
@@ -1183,18 +1103,7 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_fwd16_kernel(
             const uint64_t ix = ibase[ps] + 16 * (t0 + t4);
             float4 d;
             bool k0, k1, k2, k3;
-            if (even_T && idx32) {  // row * T even: the quad is two hash pairs
-              esp::keep_pair32(seed, (uint32_t)ix, thr, k0, k1);
-              esp::keep_pair32(seed, (uint32_t)ix + 2, thr, k2, k3);
-            } else if (even_T) {
-              esp::keep_pair(seed, ix, thr, k0, k1);
-              esp::keep_pair(seed, ix + 2, thr, k2, k3);
-            } else {
-              k0 = esp::keep_elem(seed, ix, thr);
-              k1 = esp::keep_elem(seed, ix + 1, thr);
-              k2 = esp::keep_elem(seed, ix + 2, thr);
-              k3 = esp::keep_elem(seed, ix + 3, thr);
-            }
+            keep_quad(seed, ix, thr, even_T, idx32, k0, k1, k2, k3);
             d.x = k0 ? v.x * dscale : 0.f;
             d.y = k1 ? v.y * dscale : 0.f;
             d.z = k2 ? v.z * dscale : 0.f;
@@ -1544,7 +1453,8 @@ __global__ __launch_bounds__(256, 2) void relpos_probs_lds_kernel(
     for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
     inv[r] = v > 0.f ? 1.0f / v : 0.f;
   }
-  // probabilities -> HBM through the per-wave LDS transpose (relpos_attn_fwd16_kernel's tail)
+  // probabilities -> HBM through the per-wave LDS transpose (a copy of relpos_attn_fwd16_kernel's tail, as is the
+  // softmax above: change both)
   float* stg = stage[wave];
   const int sr2 = lane >> 4, sc4 = 4 * (lane & 15);
   float* abase[4];
@@ -1582,18 +1492,7 @@ __global__ __launch_bounds__(256, 2) void relpos_probs_lds_kernel(
             const uint64_t ix = ibase[ps] + 16 * t4;
             float4 d;
             bool k0, k1, k2, k3;
-            if (even_T && idx32) {
-              esp::keep_pair32(seed, (uint32_t)ix, thr, k0, k1);
-              esp::keep_pair32(seed, (uint32_t)ix + 2, thr, k2, k3);
-            } else if (even_T) {
-              esp::keep_pair(seed, ix, thr, k0, k1);
-              esp::keep_pair(seed, ix + 2, thr, k2, k3);
-            } else {
-              k0 = esp::keep_elem(seed, ix, thr);
-              k1 = esp::keep_elem(seed, ix + 1, thr);
-              k2 = esp::keep_elem(seed, ix + 2, thr);
-              k3 = esp::keep_elem(seed, ix + 3, thr);
-            }
+            keep_quad(seed, ix, thr, even_T, idx32, k0, k1, k2, k3);
             d.x = k0 ? v.x * dscale : 0.f;
             d.y = k1 ? v.y * dscale : 0.f;
             d.z = k2 ? v.z * dscale : 0.f;
@@ -1615,6 +1514,46 @@ inline int gridn(long n) {
   long b = (n + 255) / 256;
   return (int)(b > 65536 ? 65536 : (b < 1 ? 1 : b));
 }
+
+// ---------------------------------------------------------------- launcher dispatch (host)
+// Run-time values -> template arguments.  dispatch_ge calls f(std::integral_constant<int, C>) with the first
+// candidate C >= v of an ascending list (the last one when v is past them all); dispatch_bool calls
+// f(std::true_type / std::false_type).  f is a generic lambda that names the kernel instantiation, so a
+// launcher instantiates exactly the product of its candidate lists.
+template <int... Cs>
+struct IntList {};
+template <int C0, int... Cs, class F>
+inline void dispatch_ge(IntList<C0, Cs...>, int v, F&& f) {
+  if constexpr (sizeof...(Cs) == 0) {
+    f(std::integral_constant<int, C0>{});
+  } else {
+    if (v <= C0) f(std::integral_constant<int, C0>{});
+    else dispatch_ge(IntList<Cs...>{}, v, f);
+  }
+}
+template <class F>
+inline void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+// the dropout arguments of a launch: the threshold on the kernels' 1/65536 grid and the matching rescale;
+// p == 0 also drops the dropout copy (pdrop, where the kernel writes one)
+struct DropArgs {
+  uint32_t thr;
+  float scale;
+};
+inline DropArgs drop_args(float drop_p) {
+  const uint32_t thr = esp::drop_threshold(drop_p);
+  return {thr, esp::drop_scale(thr)};
+}
+inline DropArgs drop_args(float drop_p, float*& pdrop) {
+  const DropArgs d = drop_args(drop_p);
+  if (!d.thr) pdrop = nullptr;
+  return d;
+}
+// sqrt(d_k) a power of two: s / sqrt(d_k) is exactly s * (1 / sqrt(d_k)) (the kernels' P2 forms)
+inline bool is_pow2(float x) { return x > 0.f && (__builtin_bit_cast(uint32_t, x) & 0x7fffffu) == 0; }
+using Per64 = IntList<1, 2, 4, 8, 16>;  // 64-column steps of a row of up to 1024 columns (softmax kernels' PER)
 
 }  // namespace
 
@@ -1710,24 +1649,19 @@ ESP_API int esp_attn_softmax_fwd(const float* ac, const float* bd, int relpos, i
   ESP_ARG_CHECK(relpos != 2 || P == Tq, "esp_attn_softmax_fwd: legacy rel-pos needs P=T");
   ESP_ARG_CHECK(lds >= Tk && (relpos == 0 || ldp >= P), "esp_attn_softmax_fwd: pitch < row length");
   ESP_ARG_CHECK(drop_p < 1.f, "dropout p must be < 1 (got %g)", (double)drop_p);
-  const uint32_t thr = esp::drop_threshold(drop_p);
-  if (!thr) pdrop = nullptr;
-  const float ds = esp::drop_scale(thr);
+  const DropArgs dr = drop_args(drop_p, pdrop);
   const long rows = (long)Z * Tq;
   dim3 grid((unsigned)((rows + 3) / 4));
   hipStream_t st = (hipStream_t)stream;
-#define ESP_SM(PER)                                                                                                 \
-  hipLaunchKernelGGL(softmax_fwd_kernel<PER>, grid, dim3(256), 0, st, ac, bd, relpos, P, sqrt_dk, klen, nb, causal, \
-                     attn, pdrop, thr, ds, (uint64_t)seed, Z, Tq, Tk, lds, ldp, esp::rng_key_ptr(), tvalid)
-  if (Tk <= 64) ESP_SM(1);
-  else if (Tk <= 128) ESP_SM(2);
-  else if (Tk <= 256) ESP_SM(4);
-  else if (Tk <= 512) ESP_SM(8);
-  else if (Tk <= 1024) ESP_SM(16);
+  if (Tk <= 1024)
+    dispatch_ge(Per64{}, (Tk + 63) / 64, [&](auto per) {
+      hipLaunchKernelGGL(softmax_fwd_kernel<decltype(per)::value>, grid, dim3(256), 0, st, ac, bd, relpos, P, sqrt_dk,
+                         klen, nb, causal, attn, pdrop, dr.thr, dr.scale, (uint64_t)seed, Z, Tq, Tk, lds, ldp,
+                         esp::rng_key_ptr(), tvalid);
+    });
   else
     hipLaunchKernelGGL(softmax_fwd_loop_kernel, grid, dim3(256), 0, st, ac, bd, relpos, P, sqrt_dk, klen, nb, causal,
-                       attn, pdrop, thr, ds, (uint64_t)seed, Z, Tq, Tk, lds, ldp, esp::rng_key_ptr(), tvalid);
-#undef ESP_SM
+                       attn, pdrop, dr.thr, dr.scale, (uint64_t)seed, Z, Tq, Tk, lds, ldp, esp::rng_key_ptr(), tvalid);
   ESP_CHECK_LAUNCH("esp_attn_softmax_fwd");
   return 0;
 }
@@ -1737,21 +1671,17 @@ ESP_API int esp_attn_softmax_bwd(const float* attn, const float* dP, float* dS, 
   ESP_ARG_CHECK(Tk >= 1, "esp_attn_softmax_bwd: Tk=%d", Tk);
   ESP_ARG_CHECK(lds >= Tk, "esp_attn_softmax_bwd: pitch < Tk");
   ESP_ARG_CHECK(drop_p < 1.f, "dropout p must be < 1 (got %g)", (double)drop_p);
-  const uint32_t thr = esp::drop_threshold(drop_p);
-  const float ds = esp::drop_scale(thr);
+  const DropArgs dr = drop_args(drop_p);
   dim3 grid((unsigned)((rows + 3) / 4));
   hipStream_t st = (hipStream_t)stream;
-#define ESP_SB(PER) \
-  hipLaunchKernelGGL(softmax_bwd_kernel<PER>, grid, dim3(256), 0, st, attn, dP, dS, thr, ds, (uint64_t)seed, sqrt_dk, rows, Tk, lds, esp::rng_key_ptr())
-  if (Tk <= 64) ESP_SB(1);
-  else if (Tk <= 128) ESP_SB(2);
-  else if (Tk <= 256) ESP_SB(4);
-  else if (Tk <= 512) ESP_SB(8);
-  else if (Tk <= 1024) ESP_SB(16);
+  if (Tk <= 1024)
+    dispatch_ge(Per64{}, (Tk + 63) / 64, [&](auto per) {
+      hipLaunchKernelGGL(softmax_bwd_kernel<decltype(per)::value>, grid, dim3(256), 0, st, attn, dP, dS, dr.thr,
+                         dr.scale, (uint64_t)seed, sqrt_dk, rows, Tk, lds, esp::rng_key_ptr());
+    });
   else
-    hipLaunchKernelGGL(softmax_bwd_loop_kernel<0>, grid, dim3(256), 0, st, attn, dP, dS, nullptr, 0L, thr, ds,
+    hipLaunchKernelGGL(softmax_bwd_loop_kernel<0>, grid, dim3(256), 0, st, attn, dP, dS, nullptr, 0L, dr.thr, dr.scale,
                        (uint64_t)seed, sqrt_dk, rows, Tk, lds, esp::rng_key_ptr(), nullptr);
-#undef ESP_SB
   ESP_CHECK_LAUNCH("esp_attn_softmax_bwd");
   return 0;
 }
@@ -1766,41 +1696,10 @@ ESP_API int esp_relshift_bwd(const float* dS, long lds, float* dbd, long ldp, in
   return 0;
 }
 
-// Fused latest rel-pos scores + softmax: q_v (Z,T,64) head-major (z = h*nb + b), p rows of
-// length ldpm with head h at column 64h (P = 2T-1 rows), ac (Z,T) pitch lds -> attn (may
-// alias ac) [+ dropout copy pdrop].
-ESP_API int esp_relpos_softmax_fwd(const float* qv, const float* p, long ldp_row, int nb, int H, const float* ac,
-                                   float sqrt_dk, const int* klen, float* attn, float* pdrop, float drop_p,
-                                   unsigned long long seed, int T, long lds, void* stream) {
-  ESP_ARG_CHECK(T >= 1 && T <= 1024 && lds >= T && nb >= 1 && H >= 1, "esp_relpos_softmax_fwd: bad sizes T=%d", T);
-  ESP_ARG_CHECK(ldp_row % 4 == 0 && ((uintptr_t)p & 15) == 0 && ((uintptr_t)qv & 15) == 0,
-                "esp_relpos_softmax_fwd: q_v / p must be 16-B aligned with ld %% 4 == 0");
-  ESP_ARG_CHECK(drop_p < 1.f, "dropout p must be < 1 (got %g)", (double)drop_p);
-  const uint32_t thr = esp::drop_threshold(drop_p);
-  if (!thr) pdrop = nullptr;
-  const float ds = esp::drop_scale(thr);
-  const int ntile = (T + RP_ROWS - 1 + 31) / 32;
-  const int WP = ntile * 32 + 4;
-  const size_t shm = (size_t)RP_ROWS * WP * sizeof(float);
-  ESP_ARG_CHECK(shm <= 65536, "esp_relpos_softmax_fwd: T=%d needs %zu B of LDS (> 64 KB)", T, shm);
-  dim3 grid((unsigned)((T + RP_ROWS - 1) / RP_ROWS), (unsigned)(nb * H));
-  hipStream_t st = (hipStream_t)stream;
-#define ESP_RP(PER)                                                                                              \
-  hipLaunchKernelGGL(relpos_softmax_fwd_kernel<PER>, grid, dim3(256), shm, st, qv, p, ldp_row, nb, H, ac, sqrt_dk, \
-                     klen, attn, pdrop, thr, ds, (uint64_t)seed, T, lds, WP, esp::rng_key_ptr())
-  if (T <= 64) ESP_RP(1);
-  else if (T <= 128) ESP_RP(2);
-  else if (T <= 256) ESP_RP(4);
-  else if (T <= 512) ESP_RP(8);
-  else ESP_RP(16);
-#undef ESP_RP
-  ESP_CHECK_LAUNCH("esp_relpos_softmax_fwd");
-  return 0;
-}
-
 // Fully fused latest rel-pos attention probabilities: ac = q_u k^T and the bd band both on the
 // MFMA inside the kernel, softmax + dropout copy -> attn / pdrop (pitch lds).  q_u, q_v (Z,T,64)
-// head-major; k rows at kmat + (b*T + j)*ldk + 64*head; p as in esp_relpos_softmax_fwd.
+// head-major (z = h*nb + b); k rows at kmat + (b*T + j)*ldk + 64*head; p: 2T-1 rows of length ldp_row, head h at
+// column 64h.
 ESP_API int esp_relpos_attn_fwd(const float* qu, const float* qv, const float* kmat, long ldk, const float* p,
                                 long ldp_row, int nb, int H, float sqrt_dk, const int* klen, float* attn, float* pdrop,
                                 float drop_p, unsigned long long seed, int T, long lds, void* stream) {
@@ -1809,9 +1708,7 @@ ESP_API int esp_relpos_attn_fwd(const float* qu, const float* qv, const float* k
                     ((uintptr_t)qu & 15) == 0 && ((uintptr_t)kmat & 15) == 0,
                 "esp_relpos_attn_fwd: operands must be 16-B aligned with ld %% 4 == 0");
   ESP_ARG_CHECK(drop_p < 1.f, "dropout p must be < 1 (got %g)", (double)drop_p);
-  const uint32_t thr = esp::drop_threshold(drop_p);
-  if (!thr) pdrop = nullptr;
-  const float ds = esp::drop_scale(thr);
+  const DropArgs dr = drop_args(drop_p, pdrop);
   const int nbd = (T + RP_ROWS - 1 + 31) / 32;
   const int WP = nbd * 32 + 4;
   const size_t shm = ((size_t)RP_ROWS * WP + 8 * RP_ROWS) * sizeof(float);
@@ -1819,21 +1716,13 @@ ESP_API int esp_relpos_attn_fwd(const float* qu, const float* qv, const float* k
   const int nta = ((T + 31) / 32 + 3) / 4;
   dim3 grid((unsigned)((T + RP_ROWS - 1) / RP_ROWS), (unsigned)(nb * H));
   hipStream_t st = (hipStream_t)stream;
-  const bool p2 = sqrt_dk > 0.f && (__builtin_bit_cast(uint32_t, sqrt_dk) & 0x7fffffu) == 0;
-#define ESP_RA(N)                                                                                                    \
-  do {                                                                                                               \
-    if (p2)                                                                                                          \
-      hipLaunchKernelGGL((relpos_attn_fwd_kernel<N, true>), grid, dim3(256), shm, st, qu, qv, kmat, ldk, p, ldp_row,  \
-                         nb, sqrt_dk, klen, attn, pdrop, thr, ds, (uint64_t)seed, T, lds, WP, esp::rng_key_ptr());    \
-    else                                                                                                             \
-      hipLaunchKernelGGL((relpos_attn_fwd_kernel<N, false>), grid, dim3(256), shm, st, qu, qv, kmat, ldk, p, ldp_row, \
-                         nb, sqrt_dk, klen, attn, pdrop, thr, ds, (uint64_t)seed, T, lds, WP, esp::rng_key_ptr());    \
-  } while (0)
-  if (nta <= 1) ESP_RA(1);
-  else if (nta == 2) ESP_RA(2);
-  else if (nta == 3) ESP_RA(3);
-  else ESP_RA(4);
-#undef ESP_RA
+  dispatch_ge(IntList<1, 2, 3, 4>{}, nta, [&](auto n) {
+    dispatch_bool(is_pow2(sqrt_dk), [&](auto p2) {
+      hipLaunchKernelGGL((relpos_attn_fwd_kernel<decltype(n)::value, decltype(p2)::value>), grid, dim3(256), shm, st,
+                         qu, qv, kmat, ldk, p, ldp_row, nb, sqrt_dk, klen, attn, pdrop, dr.thr, dr.scale,
+                         (uint64_t)seed, T, lds, WP, esp::rng_key_ptr());
+    });
+  });
   ESP_CHECK_LAUNCH("esp_relpos_attn_fwd");
   return 0;
 }
@@ -1853,108 +1742,59 @@ ESP_API int esp_relpos_attn_probs(const float* qu, const float* qv, const float*
                     ((uintptr_t)qu & 15) == 0 && ((uintptr_t)kmat & 15) == 0,
                 "esp_relpos_attn_probs: operands must be 16-B aligned with ld %% 4 == 0");
   ESP_ARG_CHECK(drop_p < 1.f, "dropout p must be < 1 (got %g)", (double)drop_p);
-  const uint32_t thr = esp::drop_threshold(drop_p);
-  if (!thr) pdrop = nullptr;
-  const float ds = esp::drop_scale(thr);
+  const DropArgs dr = drop_args(drop_p, pdrop);
   const int nt = (T + 15) / 16;
   const int Zn = nb * H;
   int nrb = (T + 4 * RW_ROWS - 1) / (4 * RW_ROWS);  // row blocks per z (4 waves x 16 rows)
   dim3 grid((unsigned)(8 * ((Zn + 7) / 8) * nrb));  // XCD-aware order (see the kernel)
   hipStream_t st = (hipStream_t)stream;
-  const bool p2 = sqrt_dk > 0.f && (__builtin_bit_cast(uint32_t, sqrt_dk) & 0x7fffffu) == 0;
+  // both kernels take the same arguments (nrb and grid by reference: the SPLIT 2 form below recomputes them)
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, qu, qv, kmat, ldk, p, ldp_row, nb, sqrt_dk, klen, attn, pdrop,
+                       dr.thr, dr.scale, (uint64_t)seed, T, lds, esp::rng_key_ptr(), tvalid, nrb, Zn);
+  };
+  const bool legacy = relpos == 2, p2 = is_pow2(sqrt_dk), b16 = esp_get_gemm_compute() == 1;
+  // the per-wave kernel's key-tile counts: with the block-staged kernel built in (the default) it is launched
+  // for nt > 24 only, so only those forms are instantiated; the A/B build (ESP_ATTN_PROBS_LDS=0) keeps them all
+  using WaveTiles = std::conditional_t<ESP_ATTN_PROBS_LDS != 0, IntList<28, 32>, IntList<4, 8, 12, 16, 20, 24, 28, 32>>;
+  using WaveTiles16 = std::conditional_t<ESP_ATTN_PROBS_LDS != 0, IntList<32>, IntList<8, 16, 24, 32>>;
   if (ESP_ATTN_PROBS_LDS && nt <= 24) {
     // block-staged operands, split products (relpos_probs_lds_kernel): fp32-accurate six products in
     // the fp32 mode, the single bf16 product in the bf16 mode (like every other product of its step)
-    const bool b16 = esp_get_gemm_compute() == 1;
-#define ESP_RL(N, P2_, L_, NP_)                                                                                     \
-  hipLaunchKernelGGL((relpos_probs_lds_kernel<N, P2_, L_, NP_>), grid, dim3(256), 0, st, qu, qv, kmat, ldk, p,     \
-                     ldp_row, nb, sqrt_dk, klen, attn, pdrop, thr, ds, (uint64_t)seed, T, lds, esp::rng_key_ptr(), \
-                     tvalid, nrb, Zn)
-#define ESP_RLN(N, P2_, L_)          \
-  do {                               \
-    if (b16) ESP_RL(N, P2_, L_, 1);  \
-    else ESP_RL(N, P2_, L_, 6);      \
-  } while (0)
-#define ESP_RLT(N)                                 \
-  do {                                             \
-    if (relpos == 2) {                             \
-      if (p2) ESP_RLN(N, true, true);              \
-      else ESP_RLN(N, false, true);                \
-    } else {                                       \
-      if (p2) ESP_RLN(N, true, false);             \
-      else ESP_RLN(N, false, false);               \
-    }                                              \
-  } while (0)
-    if (nt <= 8) ESP_RLT(8);
-    else if (nt <= 16) ESP_RLT(16);
-    else ESP_RLT(24);
-#undef ESP_RLT
-#undef ESP_RLN
-#undef ESP_RL
-    ESP_CHECK_LAUNCH("esp_relpos_attn_probs");
-    return 0;
+    dispatch_ge(IntList<8, 16, 24>{}, nt, [&](auto n) {
+      dispatch_bool(legacy, [&](auto l) {
+        dispatch_bool(p2, [&](auto p2c) {
+          dispatch_bool(b16, [&](auto x) {
+            launch(relpos_probs_lds_kernel<decltype(n)::value, decltype(p2c)::value, decltype(l)::value,
+                                           decltype(x)::value ? 1 : 6>);
+          });
+        });
+      });
+    });
+  } else if (b16 && legacy && nt > 16) {
+    // the bf16 mode computes the scores on bf16 operands like every other product of its step.
+    // legacy: the row-shift re-split leaves no registers for 24+ score tiles per wave; two waves
+    // share a row group's keys (SPLIT 2, half the score registers each)
+    nrb = (T + 2 * RW_ROWS - 1) / (2 * RW_ROWS);
+    grid.x = (unsigned)(8 * ((Zn + 7) / 8) * nrb);
+    dispatch_bool(p2, [&](auto p2c) { launch(relpos_attn_fwd16_kernel<16, decltype(p2c)::value, true, 2, 1>); });
+  } else if (b16) {
+    dispatch_ge(WaveTiles16{}, nt, [&](auto n) {
+      dispatch_bool(legacy, [&](auto l) {
+        dispatch_bool(p2, [&](auto p2c) {
+          launch(relpos_attn_fwd16_kernel<decltype(n)::value, decltype(p2c)::value, decltype(l)::value, 1, 1>);
+        });
+      });
+    });
+  } else {
+    dispatch_ge(WaveTiles{}, nt, [&](auto n) {
+      dispatch_bool(legacy, [&](auto l) {
+        dispatch_bool(p2, [&](auto p2c) {
+          launch(relpos_attn_fwd16_kernel<decltype(n)::value, decltype(p2c)::value, decltype(l)::value>);
+        });
+      });
+    });
   }
-  // the bf16 mode computes the scores on bf16 operands like every other product of its step
-  if (esp_get_gemm_compute() == 1) {
-#define ESP_RX(N, P2_, L_)                                                                                         \
-  hipLaunchKernelGGL((relpos_attn_fwd16_kernel<N, P2_, L_, 1, 1>), grid, dim3(256), 0, st, qu, qv, kmat, ldk, p, \
-                     ldp_row, nb, sqrt_dk, klen, attn, pdrop, thr, ds, (uint64_t)seed, T, lds, esp::rng_key_ptr(),   \
-                     tvalid, nrb, Zn)
-#define ESP_RXN(N)                      \
-  do {                                  \
-    if (relpos == 2) {                  \
-      if (p2) ESP_RX(N, true, true);    \
-      else ESP_RX(N, false, true);      \
-    } else {                            \
-      if (p2) ESP_RX(N, true, false);   \
-      else ESP_RX(N, false, false);     \
-    }                                   \
-  } while (0)
-    if (nt <= 8) ESP_RXN(8);
-    else if (nt <= 16) ESP_RXN(16);
-    else if (relpos == 2) {
-      // legacy: the row-shift re-split leaves no registers for 24+ score tiles per wave; two waves
-      // share a row group's keys (SPLIT 2, half the score registers each)
-      nrb = (T + 2 * RW_ROWS - 1) / (2 * RW_ROWS);
-      grid.x = (unsigned)(8 * ((Zn + 7) / 8) * nrb);
-      if (p2)
-        hipLaunchKernelGGL((relpos_attn_fwd16_kernel<16, true, true, 2, 1>), grid, dim3(256), 0, st, qu, qv, kmat, ldk,
-                           p, ldp_row, nb, sqrt_dk, klen, attn, pdrop, thr, ds, (uint64_t)seed, T, lds,
-                           esp::rng_key_ptr(), tvalid, nrb, Zn);
-      else
-        hipLaunchKernelGGL((relpos_attn_fwd16_kernel<16, false, true, 2, 1>), grid, dim3(256), 0, st, qu, qv, kmat, ldk,
-                           p, ldp_row, nb, sqrt_dk, klen, attn, pdrop, thr, ds, (uint64_t)seed, T, lds,
-                           esp::rng_key_ptr(), tvalid, nrb, Zn);
-    } else if (nt <= 24) ESP_RXN(24);
-    else ESP_RXN(32);
-#undef ESP_RXN
-#undef ESP_RX
-    ESP_CHECK_LAUNCH("esp_relpos_attn_probs");
-    return 0;
-  }
-#define ESP_RW3(N, P2_, L_)                                                                                         \
-  hipLaunchKernelGGL((relpos_attn_fwd16_kernel<N, P2_, L_>), grid, dim3(256), 0, st, qu, qv, kmat, ldk, p, ldp_row, \
-                     nb, sqrt_dk, klen, attn, pdrop, thr, ds, (uint64_t)seed, T, lds, esp::rng_key_ptr(), tvalid, nrb, Zn)
-#define ESP_RW(N)                             \
-  do {                                        \
-    if (relpos == 2) {                        \
-      if (p2) ESP_RW3(N, true, true);         \
-      else ESP_RW3(N, false, true);           \
-    } else {                                  \
-      if (p2) ESP_RW3(N, true, false);        \
-      else ESP_RW3(N, false, false);          \
-    }                                         \
-  } while (0)
-  if (nt <= 4) ESP_RW(4);
-  else if (nt <= 8) ESP_RW(8);
-  else if (nt <= 12) ESP_RW(12);
-  else if (nt <= 16) ESP_RW(16);
-  else if (nt <= 20) ESP_RW(20);
-  else if (nt <= 24) ESP_RW(24);
-  else if (nt <= 28) ESP_RW(28);
-  else ESP_RW(32);
-#undef ESP_RW
-#undef ESP_RW3
   ESP_CHECK_LAUNCH("esp_relpos_attn_probs");
   return 0;
 }
@@ -1970,24 +1810,16 @@ ESP_API int esp_attn_softmax_bwd_relpos_band(const float* attn, const float* dP,
   ESP_ARG_CHECK(((uintptr_t)attn & 15) == 0 && ((uintptr_t)dP & 15) == 0 && ((uintptr_t)dS & 15) == 0,
                 "esp_attn_softmax_bwd_relpos_band: attn / dP / dS must be 16-B aligned");
   ESP_ARG_CHECK(drop_p < 1.f, "dropout p must be < 1 (got %g)", (double)drop_p);
-  const uint32_t thr = esp::drop_threshold(drop_p);
-  const float ds = esp::drop_scale(thr);
+  const DropArgs dr = drop_args(drop_p);
   dim3 grid((unsigned)((rows + 3) / 4));
   hipStream_t st = (hipStream_t)stream;
-  const bool p2 = sqrt_dk > 0.f && (__builtin_bit_cast(uint32_t, sqrt_dk) & 0x7fffffu) == 0;
-#define ESP_SBB(Q)                                                                                                 \
-  do {                                                                                                             \
-    if (p2)                                                                                                        \
-      hipLaunchKernelGGL((softmax_bwd_relpos4_kernel<Q, 3, true>), grid, dim3(256), 0, st, attn, dP, dS, dbd, ldp,  \
-                         thr, ds, (uint64_t)seed, sqrt_dk, rows, T, lds, esp::rng_key_ptr(), nullptr);             \
-    else                                                                                                           \
-      hipLaunchKernelGGL((softmax_bwd_relpos4_kernel<Q, 3, false>), grid, dim3(256), 0, st, attn, dP, dS, dbd, ldp, \
-                         thr, ds, (uint64_t)seed, sqrt_dk, rows, T, lds, esp::rng_key_ptr(), nullptr);             \
-  } while (0)
-  if (T <= 256) ESP_SBB(1);
-  else if (T <= 512) ESP_SBB(2);
-  else ESP_SBB(4);
-#undef ESP_SBB
+  dispatch_ge(IntList<1, 2, 4>{}, (T + 255) / 256, [&](auto q) {
+    dispatch_bool(is_pow2(sqrt_dk), [&](auto p2) {
+      hipLaunchKernelGGL((softmax_bwd_relpos4_kernel<decltype(q)::value, 3, decltype(p2)::value>), grid, dim3(256), 0,
+                         st, attn, dP, dS, dbd, ldp, dr.thr, dr.scale, (uint64_t)seed, sqrt_dk, rows, T, lds,
+                         esp::rng_key_ptr(), nullptr);
+    });
+  });
   ESP_CHECK_LAUNCH("esp_attn_softmax_bwd_relpos_band");
   return 0;
 }
@@ -1999,56 +1831,34 @@ ESP_API int esp_attn_softmax_bwd_relpos(const float* attn, const float* dP, floa
   ESP_ARG_CHECK(T >= 1 && lds >= T && ldp >= (relpos == 1 ? 2 * T - 1 : T) && rows % T == 0,
                 "esp_attn_softmax_bwd_relpos: bad sizes");
   ESP_ARG_CHECK(drop_p < 1.f, "dropout p must be < 1 (got %g)", (double)drop_p);
-  const uint32_t thr = esp::drop_threshold(drop_p);
-  const float ds = esp::drop_scale(thr);
+  const DropArgs dr = drop_args(drop_p);
   dim3 grid((unsigned)((rows + 3) / 4));
   hipStream_t st = (hipStream_t)stream;
-  const bool p2 = sqrt_dk > 0.f && (__builtin_bit_cast(uint32_t, sqrt_dk) & 0x7fffffu) == 0;
+  const bool latest = relpos == 1;  // the kernels' R: 1 latest, 2 legacy
   if (T <= 1024 && lds % 4 == 0 && ((uintptr_t)attn & 15) == 0 && ((uintptr_t)dP & 15) == 0 &&
       ((uintptr_t)dS & 15) == 0) {
-#define ESP_SB4(Q, R)                                                                                             \
-  do {                                                                                                            \
-    if (p2)                                                                                                       \
-      hipLaunchKernelGGL((softmax_bwd_relpos4_kernel<Q, R, true>), grid, dim3(256), 0, st, attn, dP, dS, dbd, ldp, \
-                         thr, ds, (uint64_t)seed, sqrt_dk, rows, T, lds, esp::rng_key_ptr(), tvalid);                     \
-    else                                                                                                          \
-      hipLaunchKernelGGL((softmax_bwd_relpos4_kernel<Q, R, false>), grid, dim3(256), 0, st, attn, dP, dS, dbd,     \
-                         ldp, thr, ds, (uint64_t)seed, sqrt_dk, rows, T, lds, esp::rng_key_ptr(), tvalid);                \
-  } while (0)
-#define ESP_SB4R(Q)              \
-  do {                           \
-    if (relpos == 1) ESP_SB4(Q, 1); \
-    else ESP_SB4(Q, 2);          \
-  } while (0)
-    if (T <= 256) ESP_SB4R(1);
-    else if (T <= 512) ESP_SB4R(2);
-    else ESP_SB4R(4);
-#undef ESP_SB4R
-#undef ESP_SB4
-    ESP_CHECK_LAUNCH("esp_attn_softmax_bwd_relpos");
-    return 0;
+    dispatch_ge(IntList<1, 2, 4>{}, (T + 255) / 256, [&](auto q) {
+      dispatch_bool(latest, [&](auto l) {
+        dispatch_bool(is_pow2(sqrt_dk), [&](auto p2) {
+          hipLaunchKernelGGL((softmax_bwd_relpos4_kernel<decltype(q)::value, decltype(l)::value ? 1 : 2, decltype(p2)::value>),
+                             grid, dim3(256), 0, st, attn, dP, dS, dbd, ldp, dr.thr, dr.scale, (uint64_t)seed, sqrt_dk,
+                             rows, T, lds, esp::rng_key_ptr(), tvalid);
+        });
+      });
+    });
+  } else {
+    dispatch_bool(latest, [&](auto l) {
+      if (T <= 1024)
+        dispatch_ge(Per64{}, (T + 63) / 64, [&](auto per) {
+          hipLaunchKernelGGL((softmax_bwd_relpos_kernel<decltype(per)::value, decltype(l)::value ? 1 : 2>), grid, dim3(256), 0,
+                             st, attn, dP, dS, dbd, ldp, dr.thr, dr.scale, (uint64_t)seed, sqrt_dk, rows, T, lds,
+                             esp::rng_key_ptr(), tvalid);
+        });
+      else
+        hipLaunchKernelGGL(softmax_bwd_loop_kernel<decltype(l)::value ? 1 : 2>, grid, dim3(256), 0, st, attn, dP, dS, dbd, ldp,
+                           dr.thr, dr.scale, (uint64_t)seed, sqrt_dk, rows, T, lds, esp::rng_key_ptr(), tvalid);
+    });
   }
-#define ESP_SBR(PER)                                                                                         \
-  do {                                                                                                       \
-    if (relpos == 1)                                                                                         \
-      hipLaunchKernelGGL((softmax_bwd_relpos_kernel<PER, 1>), grid, dim3(256), 0, st, attn, dP, dS, dbd, ldp, \
-                         thr, ds, (uint64_t)seed, sqrt_dk, rows, T, lds, esp::rng_key_ptr(), tvalid);                \
-    else                                                                                                     \
-      hipLaunchKernelGGL((softmax_bwd_relpos_kernel<PER, 2>), grid, dim3(256), 0, st, attn, dP, dS, dbd, ldp, \
-                         thr, ds, (uint64_t)seed, sqrt_dk, rows, T, lds, esp::rng_key_ptr(), tvalid);                \
-  } while (0)
-  if (T <= 64) ESP_SBR(1);
-  else if (T <= 128) ESP_SBR(2);
-  else if (T <= 256) ESP_SBR(4);
-  else if (T <= 512) ESP_SBR(8);
-  else if (T <= 1024) ESP_SBR(16);
-  else if (relpos == 1)
-    hipLaunchKernelGGL(softmax_bwd_loop_kernel<1>, grid, dim3(256), 0, st, attn, dP, dS, dbd, ldp, thr, ds,
-                       (uint64_t)seed, sqrt_dk, rows, T, lds, esp::rng_key_ptr(), tvalid);
-  else
-    hipLaunchKernelGGL(softmax_bwd_loop_kernel<2>, grid, dim3(256), 0, st, attn, dP, dS, dbd, ldp, thr, ds,
-                       (uint64_t)seed, sqrt_dk, rows, T, lds, esp::rng_key_ptr(), tvalid);
-#undef ESP_SBR
   ESP_CHECK_LAUNCH("esp_attn_softmax_bwd_relpos");
   return 0;
 }
@@ -2063,19 +1873,14 @@ ESP_API int esp_relpos_attn_bwd(const float* dctx, long ldd, const float* vmat, 
   ESP_ARG_CHECK(ldd % 4 == 0 && ldv % 4 == 0 && ((uintptr_t)dctx & 15) == 0 && ((uintptr_t)vmat & 15) == 0,
                 "esp_relpos_attn_bwd: dctx / v must be 16-B aligned with ld %% 4 == 0");
   ESP_ARG_CHECK(drop_p < 1.f, "dropout p must be < 1 (got %g)", (double)drop_p);
-  const uint32_t thr = esp::drop_threshold(drop_p);
-  const float ds = esp::drop_scale(thr);
+  const DropArgs dr = drop_args(drop_p);
   const int nta = ((T + 31) / 32 + 3) / 4;
   dim3 grid((unsigned)((T + RP_ROWS - 1) / RP_ROWS), (unsigned)(nb * H));
   hipStream_t st = (hipStream_t)stream;
-#define ESP_RB(N)                                                                                                  \
-  hipLaunchKernelGGL(relpos_attn_bwd_kernel<N>, grid, dim3(256), 0, st, dctx, ldd, vmat, ldv, attn, dS, dbd, ldp, nb, \
-                     sqrt_dk, thr, ds, (uint64_t)seed, T, lds, esp::rng_key_ptr())
-  if (nta <= 1) ESP_RB(1);
-  else if (nta == 2) ESP_RB(2);
-  else if (nta == 3) ESP_RB(3);
-  else ESP_RB(4);
-#undef ESP_RB
+  dispatch_ge(IntList<1, 2, 3, 4>{}, nta, [&](auto n) {
+    hipLaunchKernelGGL(relpos_attn_bwd_kernel<decltype(n)::value>, grid, dim3(256), 0, st, dctx, ldd, vmat, ldv, attn,
+                       dS, dbd, ldp, nb, sqrt_dk, dr.thr, dr.scale, (uint64_t)seed, T, lds, esp::rng_key_ptr());
+  });
   ESP_CHECK_LAUNCH("esp_relpos_attn_bwd");
   return 0;
 }

@@ -1049,13 +1049,6 @@ def attn_softmax_fwd(ac, bd, relpos, P, sqrt_dk, klen_i32, nb, causal, attn, pdr
                  _p(attn), _p(pdrop), float(drop_p), seed, Z, Tq, Tk, lds or Tk, ldp or max(P, 1), _p(tvalid), _st())
 
 
-def relpos_softmax_fwd(q_v, p, ldp_row, nb, H, ac, sqrt_dk, klen_i32, attn, pdrop, drop_p, seed, T, lds):
-    """Fused latest rel-pos bd window (MFMA) + rel_shift + masked softmax + dropout copy."""
-    _f32(q_v, p, ac, attn, pdrop)
-    _native.call("esp_relpos_softmax_fwd", _p(q_v), _p(p), ldp_row, nb, H, _p(ac), float(sqrt_dk), _p(klen_i32),
-                 _p(attn), _p(pdrop), float(drop_p), int(seed) & (2 ** 64 - 1), T, lds, _st())
-
-
 def relpos_attn_fwd(q_u, q_v, kmat, ldk, p, ldp_row, nb, H, sqrt_dk, klen_i32, attn, pdrop, drop_p, seed, T, lds,
                     k_off=0):
     """Fused latest rel-pos attention probabilities (ac and the bd band on the MFMA in-kernel)."""
@@ -1112,14 +1105,97 @@ def attn_dscores(dctx, ldd, vmat, ldv, attn, dot, dS, dbd, ldp, relpos, nb, H, d
                       (8.0 if dbd is not None else 4.0) * T * T * nb * H))
 
 
+# ----------------------------------------------------------------------------- rel-pos attention: path selection
+# Every choice between the rel-pos attention kernels is made here, once per forward, by relpos_attn_paths():
+# five module flags (opt-in forms kept for A/B measurements and for the tests of those paths; read at call time,
+# the tests monkeypatch them), four shape predicates and the compute mode.
+#
+# FLASH_ATTN = True: flash-style rel-pos attention (csrc/flash_relpos.hip), d_k = 64, T <= 512, latest and
+# legacy.  Opt-in: in fp32 at T' = 374 the recompute it trades for the (Z,T,T) probability traffic costs about
+# what that traffic did (fp32 MFMA is 157 TF against 8 TB/s: 32 flop per P byte at d_k = 64), and measured per
+# layer at C2 B=128 (tools/flash_bench.py): forward 0.84 vs 0.99 ms (flash wins), backward 2.10 vs 1.79 ms
+# (materialised wins) -> off.
+FLASH_ATTN = False
+# ATTN_FWD32 = True: the 32-row-block fused forward (relpos_attn_fwd_kernel, latest only) instead of
+# the 16-row-wave kernel (esp_relpos_attn_probs); kept for A/B measurements
+ATTN_FWD32 = False
+# FUSED_ATTN_BWD = True: dP = dctx v^T on the MFMA inside the softmax / rel_shift adjoint kernel
+# (esp_relpos_attn_bwd, latest only).  It measures slower than the K=64 GEMM + the row-wise adjoint pass at C2
+# (198 vs 157 us per layer): opt-in until it is reworked
+FUSED_ATTN_BWD = False
+# ATTN_DSCORES = True: the softmax / rel_shift adjoints in the dP GEMM's epilogue (esp_attn_dscores,
+# FlashAttention-2's row dot) WITH the dbd scatter, instead of the dP GEMM + the row-wise adjoint pass, for
+# the paths that still form dbd (legacy, RELPOS_BWD_DS off).  Opt-in: measured at C2 B=128 it is 412 + 73 us
+# per layer against 59 + 266 (the epilogue's rel_shift scatter is one scalar store per element; the row-wise
+# pass writes each shifted bd row contiguously).  The default latest backward (RELPOS_BWD_DS) uses the same
+# epilogue without dbd: 648 us per layer at C2 B=384 against 316 + 657 for the GEMM + row-wise pass it replaces
+# (DESIGN 3.4) -- still 3x its memory floor, so the scatter was not the epilogue's whole cost.
+ATTN_DSCORES = False
+# RELPOS_BWD_DS = True (default): the latest rel-pos attention backward reads dS directly -- the score gradient
+# from the dP GEMM's epilogue without the dbd scatter (esp_attn_dscores, dbd None), dq = dS k + Dbd p in one
+# kernel over the staged dS rows (esp_relpos_dq) and dp along dS's diagonals (esp_relpos_dp): no dP, dbd or
+# dq_v tensor.  False: the row-wise adjoint pass + dbd band (A/B measurements, and the tests of that path).
+RELPOS_BWD_DS = True
+
+
+def flash_ok(T: int, dk: int) -> bool:
+    return FLASH_ATTN and dk == 64 and 1 <= T <= 512
+
+
 def relpos_probs_ok(T: int, dk: int) -> bool:
     """Whether esp_relpos_attn_probs covers this shape (d_k 64, T <= 512)."""
     return dk == 64 and T <= 512
 
 
 def relpos_fused_ok(T: int, dk: int) -> bool:
-    """Whether esp_relpos_softmax_fwd covers this shape (d_k 64, 32-row window in 64 KB LDS)."""
+    """Whether the 32-row-block kernels esp_relpos_attn_fwd and esp_relpos_attn_bwd cover this shape: d_k 64,
+    the 32-row band window (+ the forward's row partials) in 64 KB of LDS (T <= 449)."""
     return dk == 64 and (32 * (32 * ((T + 62) // 32) + 4) + 256) * 4 <= 65536
+
+
+def relpos_bwd_ds_ok(T: int, dk: int) -> bool:
+    """Whether the dS-only backward covers this shape: d_k 64, the 32 staged dS rows in 64 KB of LDS
+    (T <= 480), score pitch % 4 == 0 (always, with SCORE_ALIGN 4)."""
+    return dk == 64 and 1 <= T <= 480 and pitch(T) % 4 == 0
+
+
+def relpos_attn_paths(T: int, dk: int, legacy: bool, bucketed: bool):
+    """(fwd, bwd, ctx_fp32) of one rel-pos attention call; first match wins in each list.  bucketed: a legacy
+    batch padded to a length bucket (its rel_shift is taken at the device-side T', which only the materialised
+    kernels read).  The flags and predicates are looked up when called (the tests replace them).
+
+    fwd  "flash"    FLASH_ATTN, d_k 64, 1 <= T <= 512, not bucketed       esp_relpos_flash_fwd (bwd "flash" too)
+         "probs"    relpos_probs_ok, not ATTN_FWD32                       esp_relpos_attn_probs
+         "block32"  latest, relpos_fused_ok                               esp_relpos_attn_fwd
+         "gemm"     otherwise                                             ac GEMM, bd GEMM, esp_attn_softmax_fwd
+    bwd  "ds"       latest, RELPOS_BWD_DS, relpos_bwd_ds_ok, fp32 compute, neither FUSED_ATTN_BWD nor
+                    ATTN_DSCORES                                          dS-only: no dP, dbd or dq_v tensor
+         "fused"    latest, relpos_fused_ok, FUSED_ATTN_BWD               esp_relpos_attn_bwd
+         "dscores"  ATTN_DSCORES, not bucketed                            esp_attn_dscores with the dbd scatter
+         "rowpass"  otherwise                                             dP GEMM + the row-wise adjoint pass
+    ctx_fp32 = ATTN_DSCORES or bwd == "ds": the score-gradient epilogue reads ctx in fp32 (else the materialised
+    paths write ctx as planes).  It follows the flag, not the "dscores" decision: a bucketed batch keeps the
+    fp32 ctx.  (The flash kernel's ctx is fp32 always.)"""
+    if flash_ok(T, dk) and not bucketed:
+        fwd = "flash"
+    elif relpos_probs_ok(T, dk) and not ATTN_FWD32:
+        fwd = "probs"
+    elif not legacy and relpos_fused_ok(T, dk):
+        fwd = "block32"
+    else:
+        fwd = "gemm"
+    if fwd == "flash":
+        bwd = "flash"
+    elif (not legacy and RELPOS_BWD_DS and relpos_bwd_ds_ok(T, dk) and not FUSED_ATTN_BWD and not ATTN_DSCORES
+          and _COMPUTE[0] == GEMM_FP32):
+        bwd = "ds"
+    elif not legacy and relpos_fused_ok(T, dk) and FUSED_ATTN_BWD:
+        bwd = "fused"
+    elif ATTN_DSCORES and not bucketed:
+        bwd = "dscores"
+    else:
+        bwd = "rowpass"
+    return fwd, bwd, bool(ATTN_DSCORES or bwd == "ds")
 
 
 def attn_softmax_bwd(attn, dP, dS, drop_p, seed, sqrt_dk, rows, Tk, lds=None):
@@ -1153,19 +1229,6 @@ def relpos_dqv(dbd, ldp, p, ldpm, out, ldo, nb, H, T):
     if _PROF is not None:  # algorithmic work: the band only (T x T of the 2T-1 columns per row)
         ev1.record()
         _PROF.append((2.0 * T * 64 * T * nb * H, ev0, ev1, (KC, RC, T, 64, T, nb * H, "band"), 0.0))
-
-
-# RELPOS_BWD_DS = True (default): the latest rel-pos attention backward reads dS directly -- the score gradient
-# from the dP GEMM's epilogue without the dbd scatter (esp_attn_dscores, dbd None), dq = dS k + Dbd p in one
-# kernel over the staged dS rows (esp_relpos_dq) and dp along dS's diagonals (esp_relpos_dp): no dP, dbd or
-# dq_v tensor.  False: the row-wise adjoint pass + dbd band (A/B measurements, and the tests of that path).
-RELPOS_BWD_DS = True
-
-
-def relpos_bwd_ds_ok(T: int, dk: int) -> bool:
-    """Whether the dS-only backward covers this shape: d_k 64, the 32 staged dS rows in 64 KB of LDS
-    (T <= 480), score pitch % 4 == 0 (always, with SCORE_ALIGN 4)."""
-    return dk == 64 and 1 <= T <= 480 and pitch(T) % 4 == 0
 
 
 def relpos_dq(dS, lds, kmat, ldk, p, ldpm, dq, ldq, bias_part, nb, H, T, k_off=0, dq_off=0):
@@ -1216,18 +1279,6 @@ def relpos_band_buffer(Z, T, Pp, device):
     return buf
 
 
-FUSED_ATTN_BWD = False
-# ATTN_FWD32 = True: the 32-row-block fused forward (relpos_attn_fwd_kernel, latest only) instead of
-# the 16-row-wave kernel (esp_relpos_attn_probs); kept for A/B measurements
-ATTN_FWD32 = False
-# ATTN_DSCORES = True: the softmax / rel_shift adjoints in the dP GEMM's epilogue (esp_attn_dscores,
-# FlashAttention-2's row dot) WITH the dbd scatter, instead of the dP GEMM + the row-wise adjoint pass, for
-# the paths that still form dbd (legacy, RELPOS_BWD_DS off).  Opt-in: measured at C2 B=128 it is 412 + 73 us
-# per layer against 59 + 266 (the epilogue's rel_shift scatter is one scalar store per element; the row-wise
-# pass writes each shifted bd row contiguously).  The default latest backward (RELPOS_BWD_DS) uses the same
-# epilogue without dbd: 648 us per layer at C2 B=384 against 316 + 657 for the GEMM + row-wise pass it replaces
-# (DESIGN 3.4) -- still 3x its memory floor, so the scatter was not the epilogue's whole cost.
-ATTN_DSCORES = False
 def relpos_attn_bwd(dctx, ldd, vmat, ldv, attn, dS, dbd, ldp, nb, H, sqrt_dk, drop_p, seed, T, lds, v_off=0):
     """Fused latest rel-pos attention backward: dP = dctx V^T (MFMA), dropout/softmax/rel_shift adjoints."""
     _f32(dctx, vmat, attn, dS, dbd)
@@ -1235,17 +1286,7 @@ def relpos_attn_bwd(dctx, ldd, vmat, ldv, attn, dS, dbd, ldp, nb, H, sqrt_dk, dr
                  float(sqrt_dk), float(drop_p), int(seed) & (2 ** 64 - 1), T, lds, _st())
 
 
-# Flash-style rel-pos attention (csrc/flash_relpos.hip), d_k = 64, T <= 512, latest and legacy.
-# Opt-in (FLASH_ATTN = True): in fp32 at T' = 374 the recompute it trades for the (Z,T,T)
-# probability traffic costs about what that traffic did (fp32 MFMA is 157 TF against 8 TB/s:
-# 32 flop per P byte at d_k = 64), and measured per layer at C2 B=128 (tools/flash_bench.py):
-# forward 0.84 vs 0.99 ms (flash wins), backward 2.10 vs 1.79 ms (materialised wins) -> off.
-FLASH_ATTN = False
 _DP_WS = _Workspace()
-
-
-def flash_ok(T: int, dk: int) -> bool:
-    return FLASH_ATTN and dk == 64 and 1 <= T <= 512
 
 
 def relpos_flash_fwd(q_u, q_v, kmat, ldk, vmat, ldv, p, ldp_row, rel, nb, H, sqrt_dk, klen_i32, ctx, ldc, stats,

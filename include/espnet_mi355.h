@@ -361,20 +361,15 @@ int esp_relpos_dp(const float* dS, long lds, const float* qv, int rel, int nb, i
  * into the pos_bias_u / pos_bias_v gradients. */
 int esp_relpos_dq(const float* dS, long lds, const float* kmat, long ldk, const float* p, long ldpm, float* dq,
                   long ldq, float* bias_part, int nb, int H, int T, void* stream);
-/* Fused latest rel-pos scores + softmax (attention.py:240-263 with the latest rel_shift,
- * embedding.py:173-244): bd_shift[i][j] = q_v[i] . p[j + T-1-i] is computed on the MFMA per
- * 32-row block inside the kernel (no (Z,T,2T-1) bd tensor), then s = (ac + bd_shift)/sqrt(dk),
- * key mask j < klen[b], softmax, dropout copy.  q_v (Z,T,64) head-major z = h*nb + b;
- * p: P = 2T-1 rows of pitch ldp_row, head h at column 64h.  d_k must be 64; T such that the
- * 32 x (32*ceil((T+31)/32)+4) float window fits 64 KB (T <= 449).  attn may alias ac. */
-int esp_relpos_softmax_fwd(const float* qv, const float* p, long ldp_row, int nb, int H, const float* ac,
-                           float sqrt_dk, const int* klen, float* attn, float* pdrop, float drop_p,
-                           unsigned long long seed, int T, long lds, void* stream);
-/* Fully fused latest rel-pos attention probabilities: ac = (q+u) k^T AND the bd band on the
- * MFMA per 32-row block, softmax, dropout copy (attention.py:240-263, 64-96): no score
- * tensor other than attn / pdrop reaches HBM.  q_u, q_v (Z,T,64) head-major z = h*nb + b;
- * k row j of utterance b, head h at kmat + (b*T + j)*ldk + 64h (the fused qkv projection);
- * p as above.  Same limits as esp_relpos_softmax_fwd. */
+/* Fully fused latest rel-pos attention probabilities (attention.py:240-263 with the latest rel_shift,
+ * embedding.py:173-244; 64-96): ac = (q+u) k^T AND the bd band bd_shift[i][j] = q_v[i] . p[j + T-1-i] on the
+ * MFMA per 32-row block, then s = (ac + bd_shift)/sqrt(dk), key mask j < klen[b], softmax, dropout copy: no
+ * score tensor other than attn / pdrop reaches HBM.  q_u, q_v (Z,T,64) head-major z = h*nb + b; k row j of
+ * utterance b, head h at kmat + (b*T + j)*ldk + 64h (the fused qkv projection); p: P = 2T-1 rows of pitch
+ * ldp_row, head h at column 64h.  d_k must be 64; T such that the 32 x (32*ceil((T+31)/32)+4) float window
+ * (+ 256 floats of row partials) fits 64 KB (T <= 449).
+ * ABI 37: esp_relpos_softmax_fwd (the same band window over an ac tensor from HBM; no caller since the fused
+ * forms) is removed. */
 int esp_relpos_attn_fwd(const float* qu, const float* qv, const float* kmat, long ldk, const float* p,
                         long ldp_row, int nb, int H, float sqrt_dk, const int* klen, float* attn,
                         float* pdrop, float drop_p, unsigned long long seed, int T, long lds,
