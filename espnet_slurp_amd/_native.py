@@ -125,6 +125,15 @@ SIGNATURES = {
     "esp_decode_attn_masked": [P, L, L, P, L, L, L, P, L, L, L, P, L, L, P, P, P, L, I, I, I, I, I, P],
     "esp_step_linear": [P, L, P, L, P, P, P, F, I, P, L, P, L, I, P, L, I, I, I, I, I, I, P],
     "esp_step_ln_act": [P, P, P, F, F, P, I, I, I, P, I, I, P],
+    "esp_block_attn_fwd": [P, P, P, L, I, I, I, F, U64, P],
+    "esp_block_attn_bwd": [P, P, P, P, L, I, I, I, F, U64, P],
+    "esp_cbt_chunk_fwd": [P, P, I, P, I, I, I, I, I, I, I, F, I, F, U64, U64, P],
+    "esp_cbt_chunk_bwd": [P, P, I, I, I, I, I, I, I, F, I, F, U64, U64, P],
+    "esp_cbt_ctx_shift_fwd": [P, I, I, I, I, P],
+    "esp_cbt_ctx_shift_bwd": [P, I, I, I, I, P],
+    "esp_cbt_unchunk_fwd": [P, P, I, I, I, I, I, I, I, P],
+    "esp_cbt_unchunk_bwd": [P, P, I, I, I, I, I, I, I, P],
+    "esp_conv1_dgrad": [P, P, P, I, I, I, I, P],
     # workspace-size queries (host arithmetic; return bytes)
     "esp_grad_norm_workspace_bytes": [L],
     "esp_layernorm_bwd_workspace_bytes": [I, I],
@@ -141,7 +150,7 @@ _RESTYPES = {"esp_last_error": ctypes.c_char_p, "esp_abi_version": I, "esp_attn_
              "esp_get_gemm_compute": I, "esp_set_splitk_mode": I,
              "esp_f32_gemm_products": I}
 _RESTYPES.update({k: L for k in SIGNATURES if k.endswith("_workspace_bytes")})
-ABI_VERSION = 37  # bumped whenever a signature in include/espnet_mi355.h changes
+ABI_VERSION = 38  # bumped whenever a signature in include/espnet_mi355.h changes
 
 _lib = None
 

@@ -700,6 +700,10 @@ class Conv2dSubsampling(nn.Module):
         """Output length of the two convolutions for T input frames (or bins)."""
         return ((T - 3) // 2 + 1 - cls.k2) // cls.s2 + 1
 
+    def out_linear(self) -> Linear:
+        """The output projection (`out.0` here; the without-pos-enc variants keep a bare `out`)."""
+        return self.out[0]
+
     def fwd(self, feats, xscale, p_drop, seeds: Seeds, training: bool):
         B, T, F = feats.shape
         D = self.odim
@@ -726,7 +730,7 @@ class Conv2dSubsampling(nn.Module):
         else:
             K.gemm(B * T2 * F2, D, 9 * D, z1, w2r, z2, mode_a=K.I2C_KC, lda=0, mode_b=K.KC, ldb=9 * D, ldc=D,
                    bias=c2.bias, act=K.ACT_RELU, ic_a=ic, b_weight=True)
-        lin = self.out[0]
+        lin = self.out_linear()
         wor = empty(D * F2 * D, like=feats)
         K.permute3(lin.weight, wor, D, D, F2)  # (n, c, f) -> (n, f, c)
         x = empty(B * T2, D, like=feats)
@@ -737,11 +741,12 @@ class Conv2dSubsampling(nn.Module):
         return x, Ctx(feats=feats, z1=z1, z1_16=z1_16 if training else None, z1bits=z1bits, w2r=w2r, z2=z2, wor=wor,
                       pd=pd, sd=sd, xscale=xscale, B=B, T=T, F=F, T1=T1, F1=F1, T2=T2, F2=F2)
 
-    def bwd(self, c, dx):
+    def bwd(self, c, dx, dfeats=None):
+        """dfeats: a (B, T, F) buffer for the feature gradient (None, as in training: not formed)."""
         D = self.odim
         B, T2, F2, T1, F1 = c.B, c.T2, c.F2, c.T1, c.F1
         c0, c2 = self.conv[0], self.conv[2]
-        lin = self.out[0]
+        lin = self.out_linear()
         dv = torch.empty_like(dx)
         K.scale_dropout(dx, dv, alpha=c.xscale, drop_p=c.pd, seed=c.sd)
         dwor = torch.zeros(D * F2 * D, dtype=torch.float32, device=dx.device)
@@ -772,7 +777,7 @@ class Conv2dSubsampling(nn.Module):
                    rowsum=c2.bias.grad)
         K.permute3(dw2r, c2.weight.grad, D, 9, D, accumulate=True)  # (o, kk, c) -> (o, c, kk)
         z1bits = c.get("z1bits")
-        if z1bits is not None and K.conv2_c1fold_ok(D):
+        if z1bits is not None and K.conv2_c1fold_ok(D) and dfeats is None:
             # conv1's weight gradient in the input gradient's epilogue: the conv1-map gradient is never stored
             K.conv2_dgrad_c1fold(dz2p, c2.weight, z1bits, c.feats, c.T, c.F, c0.weight.grad.view(D, 9), c0.bias.grad,
                                  B, T1, F1, D, dz2_16=dz2_16)
@@ -790,6 +795,8 @@ class Conv2dSubsampling(nn.Module):
             K.col2im_relu(dcol, c.z1, dz1, B, T1, F1, D)
             del dcol
         K.conv1_wgrad(c.feats, dz1, c0.weight.grad.view(D, 9), c0.bias.grad, B, c.T, c.F, D)
+        if dfeats is not None:
+            K.conv1_dgrad(dz1, c0.weight, dfeats, B, c.T, c.F, D)
 
 
 class Conv2dSubsampling6(Conv2dSubsampling):
@@ -823,7 +830,7 @@ class Conv2dSubsampling6(Conv2dSubsampling):
         z2 = empty(npix2, D, like=feats)
         K.gemm(npix2, D, KK, col, w2r, z2, mode_a=K.KC, lda=KK, mode_b=K.KC, ldb=KK, ldc=D, bias=c2.bias,
                act=K.ACT_RELU, b_weight=True)
-        lin = self.out[0]
+        lin = self.out_linear()
         wor = empty(D * F2 * D, like=feats)
         K.permute3(lin.weight, wor, D, D, F2)  # (n, c, f) -> (n, f, c)
         x = empty(B * T2, D, like=feats)
@@ -834,12 +841,12 @@ class Conv2dSubsampling6(Conv2dSubsampling):
         return x, Ctx(feats=feats, z1=z1, col=col if training else None, w2r=w2r, z2=z2, wor=wor, pd=pd, sd=sd,
                       xscale=xscale, B=B, T=T, F=F, T1=T1, F1=F1, T2=T2, F2=F2)
 
-    def bwd(self, c, dx):
+    def bwd(self, c, dx, dfeats=None):
         D = self.odim
         k, st = self.k2, self.s2
         B, T2, F2, T1, F1 = c.B, c.T2, c.F2, c.T1, c.F1
         c0, c2 = self.conv[0], self.conv[2]
-        lin = self.out[0]
+        lin = self.out_linear()
         dv = torch.empty_like(dx)
         K.scale_dropout(dx, dv, alpha=c.xscale, drop_p=c.pd, seed=c.sd)
         dwor = torch.zeros(D * F2 * D, dtype=torch.float32, device=dx.device)
@@ -861,11 +868,37 @@ class Conv2dSubsampling6(Conv2dSubsampling):
         K.col2im_relu_nhwc(dcol, c.z1, dz1, B, T1, F1, D, k, st)
         del dcol
         K.conv1_wgrad(c.feats, dz1, c0.weight.grad.view(D, 9), c0.bias.grad, B, c.T, c.F, D)
+        if dfeats is not None:
+            K.conv1_dgrad(dz1, c0.weight, dfeats, B, c.T, c.F, D)
 
 
-def make_subsampling(input_layer: str, idim: int, odim: int) -> Conv2dSubsampling:
-    """The encoders' input_layer choice (conformer_encoder.py:173-222 / transformer_encoder.py:97-140)."""
-    cls = {"conv2d": Conv2dSubsampling, "conv2d6": Conv2dSubsampling6}.get(input_layer)
+class _WithoutPosEnc:
+    """subsampling_without_posenc.py:10-61 (Conv2dSubsamplingWOPosEnc): the same convolutions, `out` a bare
+    Linear (state_dict key out.weight), no scaling, no positional step, no dropout -- callers pass xscale 1, p 0."""
+
+    def __init__(self, idim: int, odim: int):
+        super().__init__(idim, odim)
+        self.out = Linear(odim * self.f2, odim)
+
+    def out_linear(self) -> Linear:
+        return self.out
+
+
+class Conv2dSubsamplingWOPosEnc(_WithoutPosEnc, Conv2dSubsampling):
+    """kernels [3, 3], strides [2, 2]."""
+
+
+class Conv2dSubsampling6WOPosEnc(_WithoutPosEnc, Conv2dSubsampling6):
+    """kernels [3, 5], strides [2, 3]."""
+
+
+def make_subsampling(input_layer: str, idim: int, odim: int, pos_enc: bool = True) -> Conv2dSubsampling:
+    """The encoders' input_layer choice (conformer_encoder.py:173-222 / transformer_encoder.py:97-140); pos_enc
+    False: the without-pos-enc variants of the contextual block encoder."""
+    if not pos_enc:
+        cls = {"conv2d": Conv2dSubsamplingWOPosEnc, "conv2d6": Conv2dSubsampling6WOPosEnc}.get(input_layer)
+    else:
+        cls = {"conv2d": Conv2dSubsampling, "conv2d6": Conv2dSubsampling6}.get(input_layer)
     if cls is None:
         raise NotImplementedError(f"input_layer={input_layer}: conv2d and conv2d6 are built")
     return cls(idim, odim)

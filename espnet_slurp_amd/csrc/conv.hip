@@ -384,6 +384,47 @@ ESP_API int esp_conv1_wgrad(const float* x, const float* dz1, float* dW, float* 
   return 0;
 }
 
+// conv1 input gradient (the feature gradient; training never needs it: the features are data): a wave per input
+// element (b, t, f), lanes over the channels of the up to four conv1 pixels whose 3 x 3 stride-2 patch holds it.
+namespace {
+__global__ __launch_bounds__(256) void conv1_dgrad_kernel(const float* __restrict__ dz, const float* __restrict__ W,
+                                                         float* __restrict__ dx, long total, int T, int F, int T1,
+                                                         int F1, int D) {
+  const long e = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (e >= total) return;  // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const int f = (int)(e % F);
+  const long r = e / F;
+  const int t = (int)(r % T);
+  const long b = r / T;
+  float acc = 0.f;
+  for (int kt = t & 1; kt < 3 && kt <= t; kt += 2) {
+    const int t1 = (t - kt) >> 1;
+    if (t1 >= T1) continue;
+    for (int kf = f & 1; kf < 3 && kf <= f; kf += 2) {
+      const int f1 = (f - kf) >> 1;
+      if (f1 >= F1) continue;
+      const float* g = dz + ((b * T1 + t1) * F1 + f1) * D;
+      for (int o = lane; o < D; o += 64) acc = fmaf(g[o], W[o * 9 + kt * 3 + kf], acc);
+    }
+  }
+  acc = esp::wave_sum(acc);
+  if (lane == 0) dx[e] = acc;
+}
+}  // namespace
+
+ESP_API int esp_conv1_dgrad(const float* dz1, const float* W, float* dx, int B, int T, int F, int D, void* stream) {
+  ESP_ARG_CHECK(dz1 && W && dx && B >= 1 && T >= 3 && F >= 3 && D >= 1, "esp_conv1_dgrad: bad arguments B=%d T=%d F=%d D=%d",
+                B, T, F, D);
+  const int T1 = (T - 3) / 2 + 1, F1 = (F - 3) / 2 + 1;
+  const long total = (long)B * T * F;
+  ESP_ARG_CHECK((total + 3) / 4 <= 0x7fffffffL, "esp_conv1_dgrad: too many elements");
+  hipLaunchKernelGGL(conv1_dgrad_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dz1, W, dx,
+                     total, T, F, T1, F1, D);
+  ESP_CHECK_LAUNCH("esp_conv1_dgrad");
+  return 0;
+}
+
 ESP_API int esp_permute3(const float* in, float* out, int O, int Bd, int Ad, int accumulate, void* stream) {
   hipLaunchKernelGGL(permute3_kernel, dim3(gridn((long)O * Bd * Ad)), dim3(256), 0, (hipStream_t)stream, in, out, O, Bd,
                      Ad, accumulate);

@@ -1384,6 +1384,15 @@ def conv1_wgrad(x, dz1, dW, db, B, T, F, D):
     _guard_post("esp_conv1_wgrad", ws, n)
 
 
+def conv1_dgrad(dz1, W, dx, B, T, F, D):
+    """dx (B, T, F) = the feature gradient of the first subsampling convolution from dz1 (B, T1, F1, D)."""
+    _f32(dz1, W, dx)
+    T1, F1 = (T - 3) // 2 + 1, (F - 3) // 2 + 1
+    assert dz1.numel() == B * T1 * F1 * D and W.numel() == D * 9 and dx.numel() == B * T * F and dx.is_contiguous()
+    _native.call("esp_conv1_dgrad", _p(dz1), _p(W), _p(dx), B, T, F, D, _st())
+    return dx
+
+
 def permute3(inp, out, O, Bd, Ad, accumulate=False):
     _native.call("esp_permute3", _p(inp), _p(out), O, Bd, Ad, int(accumulate), _st())
 
@@ -1603,6 +1612,88 @@ def step_ln_act(x, gamma, beta, eps, y, *, pe=None, xscale=1.0, L=1, pos0=0):
     _native.call("esp_step_ln_act", _p(x), _p(gamma), _p(beta), float(eps), float(xscale), _p(pe), int(L), int(pos0),
                  pe.shape[0] if pe is not None else 0, _p(y), rows, D, _st())
     return y
+
+
+# ----------------------------------------------------------------------------- contextual block Transformer
+# The block attention of the contextual block encoder on esp_block_attn_fwd / _bwd (one fused kernel each way, no
+# score tensor); False, or a shape outside the fused kernel's limits: MultiHeadedAttention's generic kernels with a
+# key length of block_size + 1 per block (the in-repo baseline of tools/bench_cbt.py)
+CBT_ATTN_FUSED = True
+CBT_MAX_SLOTS = 64  # esp_block_attn_*: slots per sequence
+
+
+def block_attn_ok(S: int, dk: int) -> bool:
+    return 3 <= S <= CBT_MAX_SLOTS and dk in (16, 32, 64)
+
+
+def block_attn_fwd(qkv, ctx, lse, Z, S, H, dk, drop_p=0.0, seed=0):
+    """ctx (Z*S, H*dk) = softmax-attention of Z independent sequences of S slots from the fused q | k | v rows
+    (Z*S, 3*H*dk); key j valid iff j <= S - 2, query row 0 writes zeros; lse (Z*H*S) the row log-sum-exp."""
+    _f32(qkv, ctx, lse)
+    D = H * dk
+    assert qkv.is_contiguous() and ctx.is_contiguous() and lse.is_contiguous()
+    assert qkv.numel() == Z * S * 3 * D and ctx.numel() == Z * S * D and lse.numel() == Z * H * S
+    _native.call("esp_block_attn_fwd", _p(qkv), _p(ctx), _p(lse), Z, S, H, dk, float(drop_p), seed, _st())
+    return ctx
+
+
+def block_attn_bwd(qkv, dctx, lse, dqkv, Z, S, H, dk, drop_p=0.0, seed=0):
+    """dqkv (Z*S, 3*H*dk) = dq | dk | dv of block_attn_fwd for the output gradient dctx (probabilities recomputed
+    from qkv and lse, the dropout mask regenerated from the same seed)."""
+    _f32(qkv, dctx, lse, dqkv)
+    D = H * dk
+    assert qkv.is_contiguous() and dctx.is_contiguous() and lse.is_contiguous() and dqkv.is_contiguous()
+    assert qkv.numel() == Z * S * 3 * D and dctx.numel() == Z * S * D and lse.numel() == Z * H * S
+    assert dqkv.numel() == qkv.numel()
+    _native.call("esp_block_attn_bwd", _p(qkv), _p(dctx), _p(lse), _p(dqkv), Z, S, H, dk, float(drop_p), seed, _st())
+    return dqkv
+
+
+def cbt_chunk_fwd(x, pe, xs, B, T, D, bs, hop, la, nblk, xscale, ctx_pos_enc, drop_p=0.0, seed_x=0, seed_c=0):
+    """x (B, T, D) -> xs (B, nblk, bs + 2, D): the block layout of the contextual block encoder (esp_cbt_chunk_fwd)."""
+    _f32(x, pe, xs)
+    assert x.is_contiguous() and pe.is_contiguous() and xs.is_contiguous() and pe.shape[1] == D
+    assert x.numel() == B * T * D and xs.numel() == B * nblk * (bs + 2) * D
+    _native.call("esp_cbt_chunk_fwd", _p(x), _p(pe), pe.shape[0], _p(xs), B, T, D, bs, hop, la, nblk, float(xscale),
+                 int(bool(ctx_pos_enc)), float(drop_p), seed_x, seed_c, _st())
+    return xs
+
+
+def cbt_chunk_bwd(dxs, dx, B, T, D, bs, hop, la, nblk, xscale, ctx_pos_enc, drop_p=0.0, seed_x=0, seed_c=0):
+    """The adjoint of cbt_chunk_fwd as a gather: dxs (B, nblk, bs + 2, D) -> dx (B, T, D)."""
+    _f32(dxs, dx)
+    assert dxs.is_contiguous() and dx.is_contiguous()
+    assert dx.numel() == B * T * D and dxs.numel() == B * nblk * (bs + 2) * D
+    _native.call("esp_cbt_chunk_bwd", _p(dxs), _p(dx), B, T, D, bs, hop, la, nblk, float(xscale),
+                 int(bool(ctx_pos_enc)), float(drop_p), seed_x, seed_c, _st())
+    return dx
+
+
+def cbt_ctx_shift(xs, B, nblk, S, D, backward=False):
+    """In place on (B, nblk, S, D): slot 0 of block k <- the context slot of block max(k - 1, 0); backward: the
+    adjoint (slot-0 gradients move onto the context slots they were copied from, then become zero)."""
+    _f32(xs)
+    assert xs.is_contiguous() and xs.numel() == B * nblk * S * D
+    _native.call("esp_cbt_ctx_shift_bwd" if backward else "esp_cbt_ctx_shift_fwd", _p(xs), B, nblk, S, D, _st())
+    return xs
+
+
+def cbt_unchunk_fwd(xs, y, B, T, D, bs, hop, la, nblk):
+    """y (B, T, D): every output frame from the one (block, slot) that owns it."""
+    _f32(xs, y)
+    assert xs.is_contiguous() and y.is_contiguous()
+    assert y.numel() == B * T * D and xs.numel() == B * nblk * (bs + 2) * D
+    _native.call("esp_cbt_unchunk_fwd", _p(xs), _p(y), B, T, D, bs, hop, la, nblk, _st())
+    return y
+
+
+def cbt_unchunk_bwd(dy, dxs, B, T, D, bs, hop, la, nblk):
+    """dxs (B, nblk, bs + 2, D) = the scatter of dy (B, T, D), zero elsewhere (every element written)."""
+    _f32(dy, dxs)
+    assert dy.is_contiguous() and dxs.is_contiguous()
+    assert dy.numel() == B * T * D and dxs.numel() == B * nblk * (bs + 2) * D
+    _native.call("esp_cbt_unchunk_bwd", _p(dy), _p(dxs), B, T, D, bs, hop, la, nblk, _st())
+    return dxs
 
 
 def reserve_workspace(nbytes, device):

@@ -13,6 +13,7 @@ from ..asr.ctc import CTC
 from ..asr.decoder.transformer_decoder import TransformerDecoder
 from ..asr.encoder.branchformer_encoder import BranchformerEncoder
 from ..asr.encoder.conformer_encoder import ConformerEncoder
+from ..asr.encoder.contextual_block_transformer_encoder import ContextualBlockTransformerEncoder
 from ..asr.encoder.transformer_encoder import TransformerEncoder
 from ..asr.espnet_model import ESPnetASRModel
 from ..asr.specaug.specaug import SpecAug
@@ -50,7 +51,9 @@ normalize_choices = ClassChoices("normalize", dict(global_mvn=GlobalMVN, utteran
                                  default="utterance_mvn", optional=True)
 model_choices = ClassChoices("model", dict(espnet=ESPnetASRModel), default="espnet")
 encoder_choices = ClassChoices("encoder", dict(conformer=ConformerEncoder, transformer=TransformerEncoder,
-                                               branchformer=BranchformerEncoder), default="rnn")
+                                               branchformer=BranchformerEncoder,
+                                               contextual_block_transformer=ContextualBlockTransformerEncoder),
+                           default="rnn")
 decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder), default="rnn", optional=True)
 
 

@@ -566,6 +566,52 @@ int esp_step_linear(const float* x, long ldx, const float* W, long ldw, const fl
 int esp_step_ln_act(const float* x, const float* gamma, const float* beta, float eps, float xscale, const float* pe,
                     int L, int pos0, int pe_rows, float* y, int rows, int D, void* stream);
 
+/* ---- ABI 38: the contextual block Transformer encoder (csrc/cbt.hip;
+ * espnet2/asr/encoder/contextual_block_transformer_encoder.py forward_train).
+ *
+ * esp_block_attn_fwd / _bwd: self-attention over Z independent sequences of S slots, one workgroup per (sequence,
+ * head), exact fp32 FMA, nothing but ctx and the row log-sum-exp written.  qkv: (Z*S, 3*H*dk) rows q | k | v (the
+ * fused projection's output); ctx: (Z*S, H*dk); lse: Z*H*S floats.  Mask: key j takes part iff j <= S - 2; query
+ * row 0 is dead (ctx row 0 = 0, no gradient through it as a query; as a key and value it is live).  Dropout on the
+ * probabilities with the counter hash at index ((z*H + h)*64 + i)*64 + j.  The backward recomputes the
+ * probabilities from qkv and lse, regenerates the mask, and writes dq | dk | dv into dqkv (Z*S, 3*H*dk) (every
+ * element written).  3 <= S <= 64, dk 16, 32 or 64, 0 <= drop_p < 1 (else status -1); buffers 16-byte aligned.
+ *
+ * The block layout: T frames, block_size bs, hop, look_ahead la, nblk = ceil((T - bs + hop) / hop) blocks of
+ * S = bs + 2 slots; T > bs >= 1, hop >= 1, la >= 0, bs - hop - la >= 0, nblk as stated (else status -1); bs itself is
+ * not capped here (only esp_block_attn_* is limited to 64 slots).
+ * esp_cbt_chunk_fwd: x (B, T, D) -> xs (B, nblk, S, D): slot s in 1..bs of block k holds frame t = k*hop + s - 1 as
+ *   drop(x*xscale + pe[t]) (0 when t >= T), the mask keyed on (b, t, c) with seed_x so that a frame carries one mask
+ *   in every block; slot bs + 1 holds the block's context vector, the mean of x over frames [k*hop, min(k*hop + bs, T)),
+ *   taken through drop(mean*xscale + pe[k]) (mask keyed on (b, k, c) with seed_c) when ctx_pos_enc, and slot 0 the
+ *   context vector of block max(k - 1, 0).  pe: (pe_rows >= max(T, nblk), D).
+ * esp_cbt_chunk_bwd: dxs -> dx (B, T, D), a gather: every dx element sums the blocks that hold its frame and the
+ *   means whose window holds it.
+ * esp_cbt_ctx_shift_fwd (in place): xs[b, k, 0] = xs[b, max(k - 1, 0), S - 1].  _bwd (in place) is its adjoint:
+ *   dxs[b, k, S - 1] += dxs[b, k + 1, 0] (+ dxs[b, 0, 0] for k = 0), then dxs[b, :, 0] = 0.
+ * esp_cbt_unchunk_fwd: y[b, t] = xs[b, k, t - k*hop + 1], k = 0 for t < bs - la, else
+ *   min((t - (bs - la)) / hop + 1, nblk - 1).  _bwd: dxs = the one-to-one scatter of dy, 0 elsewhere (every element
+ *   written). */
+int esp_block_attn_fwd(const float* qkv, float* ctx, float* lse, long Z, int S, int H, int dk, float drop_p,
+                       unsigned long long seed, void* stream);
+int esp_block_attn_bwd(const float* qkv, const float* dctx, const float* lse, float* dqkv, long Z, int S, int H, int dk,
+                       float drop_p, unsigned long long seed, void* stream);
+int esp_cbt_chunk_fwd(const float* x, const float* pe, int pe_rows, float* xs, int B, int T, int D, int bs, int hop,
+                      int la, int nblk, float xscale, int ctx_pos_enc, float drop_p, unsigned long long seed_x,
+                      unsigned long long seed_c, void* stream);
+int esp_cbt_chunk_bwd(const float* dxs, float* dx, int B, int T, int D, int bs, int hop, int la, int nblk, float xscale,
+                      int ctx_pos_enc, float drop_p, unsigned long long seed_x, unsigned long long seed_c, void* stream);
+int esp_cbt_ctx_shift_fwd(float* xs, int B, int nblk, int S, int D, void* stream);
+int esp_cbt_ctx_shift_bwd(float* dxs, int B, int nblk, int S, int D, void* stream);
+int esp_cbt_unchunk_fwd(const float* xs, float* y, int B, int T, int D, int bs, int hop, int la, int nblk, void* stream);
+int esp_cbt_unchunk_bwd(const float* dy, float* dxs, int B, int T, int D, int bs, int hop, int la, int nblk,
+                        void* stream);
+
+/* esp_conv1_dgrad (csrc/conv.hip): the feature gradient of the subsampling's first convolution (3 x 3, stride 2),
+ * dx (B, T, F) = the adjoint of conv1 applied to dz1 (B, T1, F1, D) (ReLU mask already applied), W (D, 9).  Training
+ * does not call it (the features are data); an encoder's run_backward forms it on request. */
+int esp_conv1_dgrad(const float* dz1, const float* W, float* dx, int B, int T, int F, int D, void* stream);
+
 /* ---- workspace sizes.  Every launcher that takes a scratch `work` buffer also takes its size
  * in bytes and fails (status -1, esp_last_error) when it is smaller than the size below, which is
  * computed by the same code that picks the launcher's chunking: callers size their buffers from
