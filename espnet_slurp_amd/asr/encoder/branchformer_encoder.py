@@ -13,8 +13,7 @@ NotImplementedError.
 """
 from __future__ import annotations
 
-import math
-from typing import List, Optional, Tuple, Union
+from typing import List, Optional, Union
 
 import torch
 from torch import nn
@@ -22,8 +21,7 @@ from torch import nn
 from ... import kernels as K
 from ...blocks import (ConvolutionalGatingMLP, Ctx, Linear, make_subsampling, LayerNorm,
                        RelPositionMultiHeadedAttention, Seeds, empty, grad_buf)
-from .abs_encoder import (AbsEncoder, EncoderFn, TooShortUttError, draw_seed, lengths_to_device, pos_table,
-                          subsampled_lengths)
+from .abs_encoder import StackedEncoder
 
 
 class BranchformerEncoderLayer(nn.Module):
@@ -98,7 +96,7 @@ class BranchformerEncoderLayer(nn.Module):
         return d
 
 
-class BranchformerEncoder(AbsEncoder):
+class BranchformerEncoder(StackedEncoder):
     def __init__(
         self,
         input_size: int,
@@ -126,8 +124,7 @@ class BranchformerEncoder(AbsEncoder):
         stochastic_depth_rate: Union[float, List[float]] = 0.0,
         max_pos_emb_len: int = 5000,
     ):
-        super().__init__()
-        self._output_size = output_size
+        super().__init__(output_size, positional_dropout_rate)
         # rel_pos_type remap, branchformer_encoder.py:328-337
         if rel_pos_type == "legacy":
             if pos_enc_layer_type == "rel_pos":
@@ -174,84 +171,16 @@ class BranchformerEncoder(AbsEncoder):
         ])
         self.after_norm = LayerNorm(output_size)
         self.dropout_rate = dropout_rate
-        self.positional_dropout_rate = positional_dropout_rate
         self.max_pos_emb_len = max_pos_emb_len
-        self.flat = None
-
-    def output_size(self) -> int:
-        return self._output_size
-
-    def attach_flat(self, flat):
-        self.flat = flat
-        for l in self.encoders:
-            if l.attn is not None:
-                l.attn.flat = flat
 
     # ---------------------------------------------------------------- explicit passes
-    def run_forward(self, feats, ilens_cpu, seeds: Seeds, training: bool, klen=None, tvalid=None):
+    def run_forward(self, feats, ilens_cpu, seeds: Seeds, training: bool, klen=None, tvalid=None, inter=None):
         """tvalid: optional device int32 (1,) = the reference batch's T' when feats are padded to a length
         bucket: frames beyond it are outside the cgMLP's depthwise window (read as its zero padding, written
         as 0) and the legacy rel_shift is taken at T'; every other op is per frame or masked by klen."""
-        B, T, _ = feats.shape
-        lim = self.embed.min_frames  # check_short_utt (subsampling.py:31-39)
-        if T < lim:
-            raise TooShortUttError(
-                f"has {T} frames and is too short for subsampling (it needs more than {lim} frames), return empty results",
-                T, lim)
-        D = self._output_size
-        olens = subsampled_lengths(ilens_cpu, T, self.embed.input_layer)
-        if klen is None:
-            klen = lengths_to_device(olens, feats.device)
-        x, c_emb = self.embed.fwd(feats, math.sqrt(D), self.positional_dropout_rate, seeds, training)
-        T2 = c_emb.T2
-        tab = pos_table("legacy" if self.legacy else "latest", T2, D, feats.device, self.max_pos_emb_len)
-        pp = self.positional_dropout_rate if training else 0.0
-        sp = seeds.next()
-        if pp > 0:
-            pos = torch.empty_like(tab)
-            K.scale_dropout(tab, pos, drop_p=pp, seed=sp)
-        else:
-            pos = tab
-        ctxs = []
-        for layer in self.encoders:
-            x, c = layer.fwd(x, pos, klen, B, T2, seeds, training, tvalid=tvalid)
-            ctxs.append(c)
-        hs, c_after = self.after_norm.fwd(x)
-        return hs.view(B, T2, D), olens, Ctx(emb=c_emb, layers=ctxs, after=c_after)
-
-    def run_backward(self, saved, dhs, grad_hook=None):
-        B, T2, D = dhs.shape
-        d = self.after_norm.bwd_new(saved.after, dhs.view(B * T2, D))
-        if grad_hook is not None:
-            grad_hook(self.after_norm)
-        for i in range(len(self.encoders) - 1, -1, -1):
-            d = self.encoders[i].bwd(saved.layers[i], d)
-            saved.layers[i] = None
-            if grad_hook is not None:
-                grad_hook(self.encoders[i])
-        self.embed.bwd(saved.emb, d)
-        if grad_hook is not None:
-            grad_hook(self.embed)
-
-    def forward(self, xs_pad: torch.Tensor, ilens: torch.Tensor, prev_states: torch.Tensor = None
-                ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
-        assert self.flat is not None, "call espnet_slurp_amd.flatten_model(model) before running"
-        ilens_cpu = ilens.detach().cpu()
-        feats = xs_pad.contiguous().float()
-        olens = subsampled_lengths(ilens_cpu, feats.shape[1], self.embed.input_layer)
-        hs = self.forward_prepared(feats, ilens_cpu, lengths_to_device(olens, feats.device), draw_seed())
-        return hs, K.h2d(olens, xs_pad.device), None
-
-    def forward_prepared(self, feats: torch.Tensor, ilens_cpu: torch.Tensor, klen: torch.Tensor, seed: int,
-                         tvalid: torch.Tensor = None):
-        """Encoder output hs (B, T', D) from device-resident inputs only (klen: int32 output
-        lengths on device): no host->device traffic, so it can be captured in a HIP graph."""
-        anchor = self.after_norm.weight
-        hook = getattr(self, "_grad_hook", None)
-        if torch.is_grad_enabled() and anchor.requires_grad:
-            return EncoderFn.apply(feats, anchor, self, ilens_cpu, seed, hook, klen, tvalid)
-        return self.run_forward(feats, ilens_cpu, Seeds(seed), self.training, klen=klen, tvalid=tvalid)[0]
-
-    def output_lengths(self, ilens_cpu: torch.Tensor, T: int) -> torch.Tensor:
-        """Valid output frames per utterance (host, no device round trip)."""
-        return subsampled_lengths(ilens_cpu, T, self.embed.input_layer)
+        assert inter is None
+        B, olens = self._begin(feats, ilens_cpu)
+        klen = self._klen(klen, olens, feats.device)
+        x, pos, c_emb = self._embed_rel(feats, seeds, training)
+        x, ctxs = self._layers_fwd(x, pos, klen, B, c_emb.T2, seeds, training, tvalid=tvalid)
+        return self._finish(x, B, olens, emb=c_emb, layers=ctxs)

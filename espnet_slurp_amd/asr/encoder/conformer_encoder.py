@@ -8,7 +8,6 @@ SLURP / LibriSpeech Conformer recipes use; anything else raises NotImplementedEr
 """
 from __future__ import annotations
 
-import math
 from typing import List, Optional, Tuple, Union
 
 import torch
@@ -16,9 +15,8 @@ from torch import nn
 
 from ... import kernels as K
 from ...blocks import (ConvolutionModule, Ctx, make_subsampling, LayerNorm, PositionwiseFeedForward,
-                       RelPositionMultiHeadedAttention, Seeds, empty)
-from .abs_encoder import (AbsEncoder, EncoderFn, TooShortUttError, draw_seed, lengths_to_device, pos_table,
-                          subsampled_lengths)
+                       RelPositionMultiHeadedAttention, Seeds)
+from .abs_encoder import StackedEncoder
 
 
 class EncoderLayer(nn.Module):
@@ -74,7 +72,7 @@ class EncoderLayer(nn.Module):
         return d
 
 
-class ConformerEncoder(AbsEncoder):
+class ConformerEncoder(StackedEncoder):
     def __init__(
         self,
         input_size: int,
@@ -105,8 +103,7 @@ class ConformerEncoder(AbsEncoder):
         layer_drop_rate: float = 0.0,
         max_pos_emb_len: int = 5000,
     ):
-        super().__init__()
-        self._output_size = output_size
+        super().__init__(output_size, positional_dropout_rate)
         # rel_pos_type remap, conformer_encoder.py:116-125
         if rel_pos_type == "legacy":
             if pos_enc_layer_type == "rel_pos":
@@ -151,7 +148,6 @@ class ConformerEncoder(AbsEncoder):
         ])
         self.after_norm = LayerNorm(output_size)
         self.dropout_rate = dropout_rate
-        self.positional_dropout_rate = positional_dropout_rate
         self.max_pos_emb_len = max_pos_emb_len
         if len(interctc_layer_idx) > 0:  # conformer_encoder.py:283-285
             assert 0 < min(interctc_layer_idx) and max(interctc_layer_idx) < num_blocks
@@ -160,16 +156,6 @@ class ConformerEncoder(AbsEncoder):
         # Linear(vocab, D) (espnet_model.py:96-101) and passes the CTC module to the forward
         self.conditioning_layer = None
         self.interctc_use_conditioning = interctc_use_conditioning
-        self.flat = None
-        self._seed_counter = 0
-
-    def output_size(self) -> int:
-        return self._output_size
-
-    def attach_flat(self, flat):
-        self.flat = flat
-        for l in self.encoders:
-            l.self_attn.flat = flat
 
     # ---------------------------------------------------------------- explicit passes
     def run_forward(self, feats, ilens_cpu, seeds: Seeds, training: bool, klen=None, tvalid=None, inter=None):
@@ -181,26 +167,10 @@ class ConformerEncoder(AbsEncoder):
         interctc_layer_idx the block output is normalised by after_norm (conformer_encoder.py:333-341) and its
         CTC loss and loss gradient are formed right here, like the heads' CTC (fused into the forward); the
         backward adds the gradient into the residual stream at that block (run_backward)."""
-        B, T, _ = feats.shape
-        lim = self.embed.min_frames  # check_short_utt (subsampling.py:31-39)
-        if T < lim:
-            raise TooShortUttError(
-                f"has {T} frames and is too short for subsampling (it needs more than {lim} frames), return empty results",
-                T, lim)
-        D = self._output_size
-        olens = subsampled_lengths(ilens_cpu, T, self.embed.input_layer)
-        if klen is None:
-            klen = lengths_to_device(olens, feats.device)
-        x, c_emb = self.embed.fwd(feats, math.sqrt(D), self.positional_dropout_rate, seeds, training)
+        B, olens = self._begin(feats, ilens_cpu)
+        klen = self._klen(klen, olens, feats.device)
+        x, pos, c_emb = self._embed_rel(feats, seeds, training)
         T2 = c_emb.T2
-        tab = pos_table("legacy" if self.legacy else "latest", T2, D, feats.device, self.max_pos_emb_len)
-        pp = self.positional_dropout_rate if training else 0.0
-        sp = seeds.next()
-        if pp > 0:
-            pos = torch.empty_like(tab)
-            K.scale_dropout(tab, pos, drop_p=pp, seed=sp)
-        else:
-            pos = tab
         ctxs = []
         inters = []
         for li, layer in enumerate(self.encoders):
@@ -209,8 +179,7 @@ class ConformerEncoder(AbsEncoder):
             if inter is not None and li + 1 in self.interctc_layer_idx:
                 x, ic = self._interctc_fwd(li + 1, x, B, T2, inter)
                 inters.append(ic)
-        hs, c_after = self.after_norm.fwd(x)
-        return hs.view(B, T2, D), olens, Ctx(emb=c_emb, layers=ctxs, after=c_after, inter=inters)
+        return self._finish(x, B, olens, emb=c_emb, layers=ctxs, inter=inters)
 
     def _interctc_fwd(self, idx, x, B, T2, inter):
         """One intermediate branch: y = after_norm(x), its CTC nll (B,) and d(weighted loss)/d logits (when the
@@ -237,8 +206,8 @@ class ConformerEncoder(AbsEncoder):
                       live=grad is not None or (prob is not None and inter["want_grad"]))
 
     def run_backward(self, saved, dhs, grad_hook=None):
-        B, T2, D = dhs.shape
-        d = self.after_norm.bwd_new(saved.after, dhs.view(B * T2, D))
+        """_layers_bwd with the intermediate branches' gradients joining the residual stream."""
+        d = self.after_norm.bwd_new(saved.after, dhs.view(-1, self._output_size))
         inter = {c.idx: c for c in (saved.get("inter") or []) if c.live}
         # after_norm (and ctc_lo) receive more gradient from the intermediate branches below: their
         # module-done hooks (the DP bucket launches) wait until the last branch is done
@@ -271,31 +240,9 @@ class ConformerEncoder(AbsEncoder):
             if self.conditioning_layer is not None:
                 grad_hook(self.conditioning_layer)
         saved.inter = None
-        self.embed.bwd(saved.emb, d)
-        if grad_hook is not None:
-            grad_hook(self.embed)
+        self._embed_bwd(saved.emb, d, grad_hook)
 
     def forward(self, xs_pad: torch.Tensor, ilens: torch.Tensor, prev_states: torch.Tensor = None,
                 ctc=None) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
-        assert self.flat is not None, "call espnet_slurp_amd.flatten_model(model) before running"
-        ilens_cpu = ilens.detach().cpu()
-        feats = xs_pad.contiguous().float()
-        olens = subsampled_lengths(ilens_cpu, feats.shape[1], self.embed.input_layer)
-        hs = self.forward_prepared(feats, ilens_cpu, lengths_to_device(olens, feats.device), draw_seed())
-        return hs, K.h2d(olens, xs_pad.device), None
-
-    def forward_prepared(self, feats: torch.Tensor, ilens_cpu: torch.Tensor, klen: torch.Tensor, seed: int,
-                         tvalid: torch.Tensor = None, inter=None):
-        """Encoder output hs (B, T', D) from device-resident inputs only (klen: int32 output
-        lengths on device): no host->device traffic, so it can be captured in a HIP graph.
-        inter: the model's intermediate-CTC request (run_forward)."""
-        anchor = self.after_norm.weight
-        hook = getattr(self, "_grad_hook", None)
-        if torch.is_grad_enabled() and anchor.requires_grad:
-            return EncoderFn.apply(feats, anchor, self, ilens_cpu, seed, hook, klen, tvalid, inter)
-        return self.run_forward(feats, ilens_cpu, Seeds(seed), self.training, klen=klen, tvalid=tvalid,
-                                inter=inter)[0]
-
-    def output_lengths(self, ilens_cpu: torch.Tensor, T: int) -> torch.Tensor:
-        """Valid output frames per utterance (host, no device round trip)."""
-        return subsampled_lengths(ilens_cpu, T, self.embed.input_layer)
+        """ctc: accepted as the reference's forward accepts it, and not read."""
+        return super().forward(xs_pad, ilens, prev_states)

@@ -26,8 +26,8 @@ from torch import nn
 from ... import kernels as K
 from ...blocks import (Ctx, LayerNorm, MultiHeadedAttention, PositionwiseFeedForward, Seeds, empty, grad_buf,
                        make_subsampling)
-from .abs_encoder import (AbsEncoder, EncoderFn, TooShortUttError, draw_seed, lengths_to_device, pos_table,
-                          subsampled_lengths)
+from .abs_encoder import StackedEncoder, pos_table
+from .transformer_encoder import TransformerEncoderLayer
 
 
 class BlockLayout:
@@ -66,24 +66,17 @@ class BlockLayout:
         return out
 
 
-class ContextualBlockEncoderLayer(nn.Module):
-    """contextual_block_encoder_layer.py:16-138 (pre-LN, no concat) on (Z*S, D) rows, Z = B*nblk."""
+class ContextualBlockEncoderLayer(TransformerEncoderLayer):
+    """contextual_block_encoder_layer.py:16-138 (pre-LN, no concat): the Transformer layer with the block mask.
+    fwd(x, klen, Z, S, seeds, training) -- klen None: block mode on (Z*S, D) rows, Z = B*nblk sequences of S slots
+    (the fixed block mask); else the plain layer over Z utterances of S frames."""
 
-    def __init__(self, size, self_attn, feed_forward, dropout_rate):
-        super().__init__()
-        self.self_attn = self_attn
-        self.feed_forward = feed_forward
-        self.norm1 = LayerNorm(size)
-        self.norm2 = LayerNorm(size)
-        self.p = dropout_rate
-        self.size = size
-
-    def _attn_fwd(self, h, resid, Z, S, klen, seeds, training):
+    def _attn_fwd(self, h, resid, klen, Z, S, seeds, training):
         a = self.self_attn
         if klen is not None or not (K.CBT_ATTN_FUSED and K.block_attn_ok(S, a.d_k)):
             if klen is None:  # block mode on the generic kernels: keys 0..bs of every block
                 klen = _block_klen(Z, S - 1, h.device)
-            return a.fwd(h, resid, Z, S, klen, False, self.p, seeds, training)
+            return super()._attn_fwd(h, resid, klen, Z, S, seeds, training)
         H, dk = a.h, a.d_k
         D = H * dk
         M = Z * S
@@ -104,7 +97,7 @@ class ContextualBlockEncoderLayer(nn.Module):
     def _attn_bwd(self, c, dout):
         a = self.self_attn
         if not c.get("fused"):
-            return a.bwd(c, dout)
+            return super()._attn_bwd(c, dout)
         H, dk = a.h, a.d_k
         D = H * dk
         dz = grad_buf(dout)
@@ -119,20 +112,6 @@ class ContextualBlockEncoderLayer(nn.Module):
         K.linear_bwd_data(dqkv, w, dx)
         return dx
 
-    def fwd(self, x, Z, S, seeds, training, klen=None):
-        """klen None: block mode (the fixed block mask); else the plain layer over Z utterances of S frames."""
-        c = Ctx()
-        h, c.ln1 = self.norm1.fwd(x)
-        x, c.mha = self._attn_fwd(h, x, Z, S, klen, seeds, training)
-        h, c.ln2 = self.norm2.fwd(x)
-        x, c.ff = self.feed_forward.fwd(h, x, 1.0, self.p, seeds, training)
-        return x, c
-
-    def bwd(self, c, d):
-        self.norm2.bwd(c.ln2, self.feed_forward.bwd(c.ff, d), d)
-        self.norm1.bwd(c.ln1, self._attn_bwd(c.mha, d), d)
-        return d
-
 
 _KLEN = {}
 
@@ -145,14 +124,14 @@ def _block_klen(Z: int, n: int, device) -> torch.Tensor:
     return t
 
 
-class ContextualBlockTransformerEncoder(AbsEncoder):
+class ContextualBlockTransformerEncoder(StackedEncoder):
     def __init__(self, input_size: int, output_size: int = 256, attention_heads: int = 4, linear_units: int = 2048,
                  num_blocks: int = 6, dropout_rate: float = 0.1, positional_dropout_rate: float = 0.1,
                  attention_dropout_rate: float = 0.0, input_layer: Optional[str] = "conv2d", pos_enc_class=None,
                  normalize_before: bool = True, concat_after: bool = False, positionwise_layer_type: str = "linear",
                  positionwise_conv_kernel_size: int = 1, padding_idx: int = -1, block_size: int = 40,
                  hop_size: int = 16, look_ahead: int = 16, init_average: bool = True, ctx_pos_enc: bool = True):
-        super().__init__()
+        super().__init__(output_size, positional_dropout_rate)
         bad = []
         if input_layer not in ("conv2d", "conv2d6"):
             bad.append(f"input_layer={input_layer}")
@@ -172,7 +151,6 @@ class ContextualBlockTransformerEncoder(AbsEncoder):
                                                    or look_ahead < 0)):
             raise ValueError(f"block_size={block_size}, hop_size={hop_size}, look_ahead={look_ahead}: need "
                              "hop_size > 0 and block_size - hop_size - look_ahead >= 0")
-        self._output_size = output_size
         self.embed = make_subsampling(input_layer, input_size, output_size, pos_enc=False)
         self.encoders = nn.ModuleList([
             ContextualBlockEncoderLayer(output_size,
@@ -180,21 +158,11 @@ class ContextualBlockTransformerEncoder(AbsEncoder):
                                         PositionwiseFeedForward(output_size, linear_units, dropout_rate, K.ACT_RELU),
                                         dropout_rate) for _ in range(num_blocks)])
         self.after_norm = LayerNorm(output_size)
-        self.positional_dropout_rate = positional_dropout_rate
         self.block_size = block_size
         self.hop_size = hop_size
         self.look_ahead = look_ahead
         self.init_average = init_average
         self.ctx_pos_enc = ctx_pos_enc
-        self.flat = None
-
-    def output_size(self) -> int:
-        return self._output_size
-
-    def attach_flat(self, flat):
-        self.flat = flat
-        for l in self.encoders:
-            l.self_attn.flat = flat
 
     def layout(self, T2: int) -> Optional[BlockLayout]:
         """The block layout of T2 subsampled frames; None: the short path (the plain Transformer stack)."""
@@ -202,37 +170,21 @@ class ContextualBlockTransformerEncoder(AbsEncoder):
             return None
         return BlockLayout(T2, self.block_size, self.hop_size, self.look_ahead)
 
-    def run_forward(self, feats, ilens_cpu, seeds: Seeds, training: bool, klen=None, tvalid=None):
+    def run_forward(self, feats, ilens_cpu, seeds: Seeds, training: bool, klen=None, tvalid=None, inter=None):
+        """klen (int32 output lengths on device) is read by the short path alone; olens come from the pad mask,
+        also in block mode."""
         if tvalid is not None:
             raise NotImplementedError(_UNSUPPORTED + "; got tvalid (length buckets)")
-        B, T, _ = feats.shape
-        lim = self.embed.min_frames  # check_short_utt (subsampling.py:31-39)
-        if T < lim:
-            raise TooShortUttError(f"has {T} frames and is too short for subsampling", T, lim)
+        assert inter is None
+        B, olens = self._begin(feats, ilens_cpu)
+        L = self.layout(self.embed.out_frames(feats.shape[1]))
+        if L is None:  # the plain Transformer stack with the pad mask
+            klen = self._klen(klen, olens, feats.device)
+            x, c_emb = self._embed_abs(feats, seeds, training)
+            x, ctxs = self._layers_fwd(x, klen, B, c_emb.T2, seeds, training)
+            return self._finish(x, B, olens, emb=c_emb, layers=ctxs, L=None)
         D = self._output_size
-        olens = subsampled_lengths(ilens_cpu, T, self.embed.input_layer)
-        L = self.layout(self.embed.out_frames(T))
         pp = self.positional_dropout_rate if training else 0.0
-        ctxs = []
-        if L is None:
-            # x*sqrt(D) from the output linear's epilogue, + pe, dropout over the whole tensor (embedding.py:81-94)
-            if klen is None:
-                klen = lengths_to_device(olens, feats.device)
-            x, c_emb = self.embed.fwd(feats, math.sqrt(D), 0.0, seeds, training)
-            T2 = c_emb.T2
-            pe = pos_table("abs", T2, D, feats.device)
-            sp = seeds.next()
-            x3 = x.view(B, T2, D)
-            y = torch.empty_like(x)
-            for b in range(B):
-                K.scale_dropout(pe, y[b * T2:(b + 1) * T2], alpha=1.0, drop_p=0.0, seed=0, r=x3[b], beta=1.0)
-            if pp > 0:
-                K.scale_dropout(y, y, drop_p=pp, seed=sp)
-            for layer in self.encoders:
-                y, c = layer.fwd(y, B, T2, seeds, training, klen=klen)
-                ctxs.append(c)
-            hs, c_after = self.after_norm.fwd(y)
-            return hs.view(B, T2, D), olens, Ctx(emb=c_emb, layers=ctxs, after=c_after, pp=pp, sp=sp, L=None)
         x, c_emb = self.embed.fwd(feats, 1.0, 0.0, seeds, training)
         T2 = c_emb.T2
         assert T2 == L.T
@@ -241,76 +193,48 @@ class ContextualBlockTransformerEncoder(AbsEncoder):
         Z, S = B * L.nblk, L.S
         y = empty(Z * S, D, like=x)
         K.cbt_chunk_fwd(x, pe, y, B, T2, D, L.bs, L.hop, L.la, L.nblk, math.sqrt(D), self.ctx_pos_enc, pp, sp, sc)
+        ctxs = []
         for i, layer in enumerate(self.encoders):
             if i > 0:  # in place, before anything keeps the buffer: slot 0 <- the previous block's context slot
                 K.cbt_ctx_shift(y, B, L.nblk, S, D)
-            y, c = layer.fwd(y, Z, S, seeds, training)
+            y, c = layer.fwd(y, None, Z, S, seeds, training)
             ctxs.append(c)
         ys = empty(B * T2, D, like=x)
         K.cbt_unchunk_fwd(y, ys, B, T2, D, L.bs, L.hop, L.la, L.nblk)
-        hs, c_after = self.after_norm.fwd(ys)
-        return hs.view(B, T2, D), olens, Ctx(emb=c_emb, layers=ctxs, after=c_after, pp=pp, sp=sp, sc=sc, L=L)
+        return self._finish(ys, B, olens, emb=c_emb, layers=ctxs, pp=pp, sp=sp, sc=sc, L=L)
 
     def run_backward(self, saved, dhs, grad_hook=None, dfeats=None):
         """dfeats: a (B, T, F) buffer that receives the feature gradient (training passes none: fbank needs none)."""
-        B, T2, D = dhs.shape
         L = saved.L
-        d = self.after_norm.bwd_new(saved.after, dhs.view(B * T2, D))
+        if L is None:
+            return self._embed_bwd(saved.emb, self._layers_bwd(saved, dhs, grad_hook), grad_hook, dfeats)
+        B, T2, D = dhs.shape
+        dy = self.after_norm.bwd_new(saved.after, dhs.view(B * T2, D))
         if grad_hook is not None:
             grad_hook(self.after_norm)
-        if L is not None:
-            dy = d
-            d = empty(B * L.nblk * L.S, D, like=dy)
-            K.cbt_unchunk_bwd(dy, d, B, T2, D, L.bs, L.hop, L.la, L.nblk)
+        d = empty(B * L.nblk * L.S, D, like=dy)
+        K.cbt_unchunk_bwd(dy, d, B, T2, D, L.bs, L.hop, L.la, L.nblk)
         for i in range(len(self.encoders) - 1, -1, -1):
             d = self.encoders[i].bwd(saved.layers[i], d)
             saved.layers[i] = None
-            if L is not None and i > 0:
+            if i > 0:
                 K.cbt_ctx_shift(d, B, L.nblk, L.S, D, backward=True)
             if grad_hook is not None:
                 grad_hook(self.encoders[i])
-        if L is None:
-            if saved.pp > 0:
-                K.scale_dropout(d, d, drop_p=saved.pp, seed=saved.sp)
-        else:
-            dx = empty(B * T2, D, like=d)
-            K.cbt_chunk_bwd(d, dx, B, T2, D, L.bs, L.hop, L.la, L.nblk, math.sqrt(D), self.ctx_pos_enc, saved.pp,
-                            saved.sp, saved.sc)
-            d = dx
-        self.embed.bwd(saved.emb, d, dfeats=dfeats)
-        if grad_hook is not None:
-            grad_hook(self.embed)
+        dx = empty(B * T2, D, like=d)
+        K.cbt_chunk_bwd(d, dx, B, T2, D, L.bs, L.hop, L.la, L.nblk, math.sqrt(D), self.ctx_pos_enc, saved.pp,
+                        saved.sp, saved.sc)
+        self._embed_bwd(saved.emb, dx, grad_hook, dfeats)
 
     def forward(self, xs_pad: torch.Tensor, ilens: torch.Tensor, prev_states: torch.Tensor = None,
                 is_final: bool = True, infer_mode: bool = False
                 ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
         if infer_mode and not self.training:
             raise NotImplementedError(_UNSUPPORTED + "; got infer_mode=True")
-        assert self.flat is not None, "call espnet_slurp_amd.flatten_model(model) before running"
-        ilens_cpu = ilens.detach().cpu()
-        feats = xs_pad.contiguous().float()
-        olens = subsampled_lengths(ilens_cpu, feats.shape[1], self.embed.input_layer)
-        hs = self.forward_prepared(feats, ilens_cpu, lengths_to_device(olens, feats.device), draw_seed())
-        return hs, K.h2d(olens, xs_pad.device), None
+        return super().forward(xs_pad, ilens, prev_states)
 
     def forward_infer(self, *args, **kwargs):
         raise NotImplementedError(_UNSUPPORTED + "; got forward_infer")
-
-    def forward_prepared(self, feats: torch.Tensor, ilens_cpu: torch.Tensor, klen: torch.Tensor, seed: int,
-                         tvalid: torch.Tensor = None):
-        """Encoder output hs (B, T', D) from device-resident inputs only (klen: int32 output lengths on device,
-        read by the short path alone): no host->device traffic, so it can be captured in a HIP graph."""
-        if tvalid is not None:
-            raise NotImplementedError(_UNSUPPORTED + "; got tvalid (length buckets)")
-        anchor = self.after_norm.weight
-        hook = getattr(self, "_grad_hook", None)
-        if torch.is_grad_enabled() and anchor.requires_grad:
-            return EncoderFn.apply(feats, anchor, self, ilens_cpu, seed, hook, klen, None)
-        return self.run_forward(feats, ilens_cpu, Seeds(seed), self.training, klen=klen)[0]
-
-    def output_lengths(self, ilens_cpu: torch.Tensor, T: int) -> torch.Tensor:
-        """Valid output frames per utterance (host, no device round trip): from the pad mask, also in block mode."""
-        return subsampled_lengths(ilens_cpu, T, self.embed.input_layer)
 
 
 _UNSUPPORTED = ("espnet_slurp_amd ContextualBlockTransformerEncoder supports input_layer conv2d / conv2d6, pre-LN, "

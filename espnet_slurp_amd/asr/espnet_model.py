@@ -312,9 +312,8 @@ class ESPnetASRModel(AbsESPnetModel):
             host["ys_in_lens"] = ys_in_lens.to(torch.int32)
         return prep
 
-    def forward_prepared(self, speech: torch.Tensor, prep: Prepared):
-        """The step's device work from a prepared batch: no host->device traffic and no host
-        synchronisation, so the forward + backward can be captured as one HIP graph."""
+    def _features(self, speech: torch.Tensor, prep: Prepared) -> torch.Tensor:
+        """frontend -> SpecAug (training) -> normalize, from the prepared batch's device tensors."""
         d = prep.dev
         if self.frontend is not None:  # raw samples -> log-mel on device (one kernel)
             feats = self.frontend.apply_prepared(speech, d["wav_lens"], prep.n_samples, d.get("nvalid"))
@@ -325,26 +324,41 @@ class ESPnetASRModel(AbsESPnetModel):
             feats = self.specaug.apply_prepared(feats, d["lens"], draws)
         if self.normalize is not None:
             feats = self.normalize.apply_prepared(feats, d["lens"])
+        return feats
+
+    def _stats(self, loss, others, inter, detach: bool):
+        """The reference's stats dict from the heads' (loss_ctc, loss_att, acc) and the intermediate branches'
+        losses; detach: the values leave the autograd graph (forward_prepared's are autograd outputs)."""
+        stats = dict(
+            loss_ctc=others[0:1] if self.ctc is not None else None,
+            cer_ctc=None,
+            loss_att=others[1:2] if self.decoder is not None else None,
+            acc=others[2:3] if self.decoder is not None else None,
+            cer=None, wer=None,
+            loss=loss,
+        )
+        if inter:
+            stats.update(inter["stats"])
+        if detach:
+            stats = {k: t if t is None else t.detach() for k, t in stats.items()}
+        return stats
+
+    def forward_prepared(self, speech: torch.Tensor, prep: Prepared):
+        """The step's device work from a prepared batch: no host->device traffic and no host
+        synchronisation, so the forward + backward can be captured as one HIP graph."""
+        d = prep.dev
+        feats = self._features(speech, prep)
         grad_on = torch.is_grad_enabled() and next(iter(self.parameters())).requires_grad
         inter = self._inter_request(prep, grad_on)
         encoder_out = self.encoder.forward_prepared(feats, prep.sl_cpu, d["hlens"], prep.enc_seed, d.get("tvalid"),
-                                                    **({"inter": inter} if inter else {}))
+                                                    inter)
         anchor = next(p for p in (self.ctc or self.decoder).parameters())
         if torch.is_grad_enabled() and anchor.requires_grad:
             loss, others = HeadsFn.apply(encoder_out, anchor, self, prep, prep.heads_seed)
         else:
             out4, _ = self._heads_forward(encoder_out, prep, Seeds(prep.heads_seed), False)
             loss, others = out4[3:4], out4[0:3]
-        stats = dict(
-            loss_ctc=others[0:1].detach() if self.ctc is not None else None,
-            cer_ctc=None,
-            loss_att=others[1:2].detach() if self.decoder is not None else None,
-            acc=others[2:3].detach() if self.decoder is not None else None,
-            cer=None, wer=None,
-            loss=loss.detach(),
-        )
-        if inter:
-            stats.update({k: v.detach() for k, v in inter["stats"].items()})
+        stats = self._stats(loss, others, inter, detach=True)
         if not self.training and self.error_calculator is not None:
             stats.update(self._error_rates(encoder_out, prep))
         return loss, stats, d["weight"]
@@ -356,32 +370,14 @@ class ESPnetASRModel(AbsESPnetModel):
         autograd engine would call from its device thread.  Same kernels, same order."""
         d = prep.dev
         with torch.no_grad():
-            if self.frontend is not None:
-                feats = self.frontend.apply_prepared(speech, d["wav_lens"], prep.n_samples, d.get("nvalid"))
-            else:
-                feats = speech[:, : prep.T].contiguous().float()
-            if self.specaug is not None and self.training:
-                draws = {k[3:]: v for k, v in d.items() if k.startswith("sa_")}
-                feats = self.specaug.apply_prepared(feats, d["lens"], draws)
-            if self.normalize is not None:
-                feats = self.normalize.apply_prepared(feats, d["lens"])
+            feats = self._features(speech, prep)
             enc = self.encoder
             inter = self._inter_request(prep, True)
             hs, _olens, saved = enc.run_forward(feats, prep.sl_cpu, Seeds(prep.enc_seed), enc.training, klen=d["hlens"],
-                                                tvalid=d.get("tvalid"), **({"inter": inter} if inter else {}))
+                                                tvalid=d.get("tvalid"), inter=inter)
             out4, state = self._heads_forward(hs, prep, Seeds(prep.heads_seed), True)
-        loss, others = out4[3:4], out4[0:3]
-        stats = dict(
-            loss_ctc=others[0:1] if self.ctc is not None else None,
-            cer_ctc=None,
-            loss_att=others[1:2] if self.decoder is not None else None,
-            acc=others[2:3] if self.decoder is not None else None,
-            cer=None, wer=None,
-            loss=loss,
-        )
-        if inter:
-            stats.update(inter["stats"])
-        return loss, stats, d["weight"], (saved, state)
+        loss = out4[3:4]
+        return loss, self._stats(loss, out4[0:3], inter, detach=False), d["weight"], (saved, state)
 
     def backward_explicit(self, ctx, g_loss: torch.Tensor, hook=None):
         """The backward of forward_explicit for d loss = g_loss (a device scalar): heads, then

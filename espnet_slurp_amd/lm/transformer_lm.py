@@ -31,7 +31,7 @@ from .. import kernels as K
 from ..asr.decoder.transformer_decoder import DecoderCache, RowState, merge_row_states
 from ..asr.encoder.abs_encoder import pos_table
 from ..asr.encoder.transformer_encoder import TransformerEncoderLayer
-from ..blocks import Ctx, LayerNorm, Linear, MultiHeadedAttention, PositionwiseFeedForward, Seeds, empty
+from ..blocks import LayerNorm, Linear, MultiHeadedAttention, PositionwiseFeedForward, Seeds, empty
 from ..flat import FlatParams
 
 
@@ -46,16 +46,6 @@ def _ln(norm: LayerNorm):
     return norm.weight, norm.bias, norm.eps
 
 
-class _CausalLayer(TransformerEncoderLayer):
-    def fwd(self, x, klen, B, T, seeds, training):
-        c = Ctx()
-        h, c.ln1 = self.norm1.fwd(x)
-        x, c.mha = self.self_attn.fwd(h, x, B, T, klen, True, self.p, seeds, training)
-        h, c.ln2 = self.norm2.fwd(x)
-        x, c.ff = self.feed_forward.fwd(h, x, 1.0, self.p, seeds, training)
-        return x, c
-
-
 class _Encoder(nn.Module):
     """Parameter layout of the espnet1 Encoder with input_layer="linear" (embed.0 Linear, embed.1 torch LayerNorm;
     embed.2-4 -- Dropout, ReLU, the positional class -- hold no parameters)."""
@@ -64,8 +54,9 @@ class _Encoder(nn.Module):
         super().__init__()
         self.embed = nn.Sequential(Linear(idim, att_unit), LayerNorm(att_unit, eps=1e-5))
         self.encoders = nn.ModuleList([
-            _CausalLayer(att_unit, MultiHeadedAttention(head, att_unit, 0.0),
-                         PositionwiseFeedForward(att_unit, unit, dropout_rate, K.ACT_RELU), dropout_rate)
+            TransformerEncoderLayer(att_unit, MultiHeadedAttention(head, att_unit, 0.0),
+                                    PositionwiseFeedForward(att_unit, unit, dropout_rate, K.ACT_RELU), dropout_rate,
+                                    causal=True)
             for _ in range(layer)])
         self.after_norm = LayerNorm(att_unit)
 

@@ -44,3 +44,20 @@ def test_gemm_shapes_trace_maps_dispatches(tmp_path):
     # conv2_dgrad: one launch of 4 class dispatches, 1 + 2 + 3 + 4 us
     assert cv[-5] == "1" and float(cv[-4]) == 0.010 and float(cv[-3]) == 0.010
     assert "12 dispatches" not in out and "(6 dispatches)" in out
+
+
+def test_launch_trace_pack_round_trip_and_kept_traces():
+    """tools/launch_trace.py: pack / unpack are inverses, and the kept packed traces unpack to the 13 cases whose
+    sha256 the kept comparison against the parent commit records."""
+    import hashlib
+    import re
+
+    from tools import launch_trace as LT
+    traces = {"a": "# train\nx 1\ny 2\nz 3\n", "b": "x 1\ny 2\nz 3\nx 1\ny 2\n# hook m\n", "c": ""}
+    packed = LT.pack(traces)
+    assert LT.unpack(packed) == traces and "@" in packed
+    kept = LT.unpack(open(os.path.join(ROOT, "profiles", "r13a_launch_traces.txt")).read())
+    assert list(kept) == list(LT.CASES)
+    want = dict(re.findall(r"^(\w+): .*sha256 ([0-9a-f]{64}), parent vs new identical$",
+                           open(os.path.join(ROOT, "profiles", "r13a_launch_trace_diff.txt")).read(), re.M))
+    assert {n: hashlib.sha256(t.encode()).hexdigest() for n, t in kept.items()} == want
