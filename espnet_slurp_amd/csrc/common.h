@@ -112,33 +112,39 @@ __device__ __forceinline__ float fast_sigmoid(float v) {
 // takes the part straight from the packed pair (no unpack): 7 VALU per pair instead of 11 (the split is
 // the in-register GEMMs' VALU bound: 11 VALU per pair ~ the MFMA time of the six products,
 // profiles/r05m_*).  The residual is exactly representable, so it is exact under any rounding of the
-// dot's sum; 0: the unpack + v_sub form.
+// dot's sum; 0: the unpack + v_sub form.  split3_pair<false> is the v_sub form in either build, for a caller
+// whose pair partners are different rows of an operand (gemm_wgrad_ws.hip): there a non-finite element must not
+// reach its partner's row.  Both forms give the same parts for finite pairs.
 #ifndef ESP_SPLIT_DOT
 #define ESP_SPLIT_DOT 1
 #endif
+template <bool DOT = (ESP_SPLIT_DOT != 0)>
 __device__ __forceinline__ void split3_pair(float a, float b, uint32_t& hi, uint32_t& mid, uint32_t& lo) {
   typedef __attribute__((ext_vector_type(2))) float f2;
   typedef __attribute__((ext_vector_type(2))) __bf16 b2;
   const b2 hp = __builtin_convertvector((f2){a, b}, b2);
-#if ESP_SPLIT_DOT
-  // the (-1, 0) / (0, -1) bf16 pairs from SGPRs: as an inline constant the assembler encodes (-1, 0) as
-  // the fp32 -1.0, which the hardware reads as the pair (0, -1)
-  uint32_t na, nb;
-  asm("s_mov_b32 %0, 0xbf80" : "=s"(na));
-  asm("s_mov_b32 %0, 0xbf800000" : "=s"(nb));
-  const b2 NA = __builtin_bit_cast(b2, na), NB = __builtin_bit_cast(b2, nb);
-  const float ra = __builtin_amdgcn_fdot2_f32_bf16(hp, NA, a, false);
-  const float rb = __builtin_amdgcn_fdot2_f32_bf16(hp, NB, b, false);
-  const b2 mp = __builtin_convertvector((f2){ra, rb}, b2);
-  const float sa = __builtin_amdgcn_fdot2_f32_bf16(mp, NA, ra, false);
-  const float sb = __builtin_amdgcn_fdot2_f32_bf16(mp, NB, rb, false);
-#else
-  const uint32_t hu = __builtin_bit_cast(uint32_t, hp);
-  const float ra = a - __uint_as_float(hu << 16), rb = b - __uint_as_float(hu & 0xffff0000u);
-  const b2 mp = __builtin_convertvector((f2){ra, rb}, b2);
-  const uint32_t mu = __builtin_bit_cast(uint32_t, mp);
-  const float sa = ra - __uint_as_float(mu << 16), sb = rb - __uint_as_float(mu & 0xffff0000u);
-#endif
+  float sa, sb;
+  b2 mp;
+  if constexpr (DOT) {
+    // the (-1, 0) / (0, -1) bf16 pairs from SGPRs: as an inline constant the assembler encodes (-1, 0) as
+    // the fp32 -1.0, which the hardware reads as the pair (0, -1)
+    uint32_t na, nb;
+    asm("s_mov_b32 %0, 0xbf80" : "=s"(na));
+    asm("s_mov_b32 %0, 0xbf800000" : "=s"(nb));
+    const b2 NA = __builtin_bit_cast(b2, na), NB = __builtin_bit_cast(b2, nb);
+    const float ra = __builtin_amdgcn_fdot2_f32_bf16(hp, NA, a, false);
+    const float rb = __builtin_amdgcn_fdot2_f32_bf16(hp, NB, b, false);
+    mp = __builtin_convertvector((f2){ra, rb}, b2);
+    sa = __builtin_amdgcn_fdot2_f32_bf16(mp, NA, ra, false);
+    sb = __builtin_amdgcn_fdot2_f32_bf16(mp, NB, rb, false);
+  } else {
+    const uint32_t hu = __builtin_bit_cast(uint32_t, hp);
+    const float ra = a - __uint_as_float(hu << 16), rb = b - __uint_as_float(hu & 0xffff0000u);
+    mp = __builtin_convertvector((f2){ra, rb}, b2);
+    const uint32_t mu = __builtin_bit_cast(uint32_t, mp);
+    sa = ra - __uint_as_float(mu << 16);
+    sb = rb - __uint_as_float(mu & 0xffff0000u);
+  }
   hi = __builtin_bit_cast(uint32_t, hp);
   mid = __builtin_bit_cast(uint32_t, mp);
   lo = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){sa, sb}, b2));

@@ -127,6 +127,10 @@ int g_last_grid = 0;  // the grid of the last LDS-DMA launch (EPI_C1FOLD: its pe
 int g_splitk = 0;
 int splitk_mode() { return g_splitk; }
 
+// gemm_wgrad_ws_kernel for the eligible RC x RC fp32 GEMMs: 0 never, 1 when its split-K grid fills the chip
+// (default), 2 whenever the launch is structurally eligible (tests: small shapes)
+int g_wgrad_ws = 1;
+
 // smallest K a split-K split keeps on grids of >= 64 tiles (128 before round 4's end)
 constexpr long kSplitkMinK = 256;
 long splitk_mink() { return kSplitkMinK; }
@@ -197,7 +201,7 @@ bool launch_glds(int MA, int MB, const GemmArgs& g, int batch, hipStream_t st, c
   const bool rs = can_rs && g.rowsum;
   if (rs) kind = EPI_PLAIN;
   if (kind == EPI_C1FOLD && !(MA == I2CT_KC && MB == RC && BNT == 128 && bm == 128 && x.ntx <= C1NT)) return false;
-  const dim3 grid((unsigned)std::min<long>(x.ntiles, persist_blocks(glds_occupancy_rt(BNT, kind, bm, g.bf16))));
+  const dim3 grid((unsigned)std::min<long>(x.ntiles, persist_blocks(g.ws ? 1 : glds_occupancy_rt(BNT, kind, bm, g.bf16))));
   g_last_grid = (int)grid.x;
   x.fd_grid = make_fastdiv(grid.x);
   x.fd_ntx = make_fastdiv((uint32_t)x.ntx);
@@ -205,6 +209,7 @@ bool launch_glds(int MA, int MB, const GemmArgs& g, int batch, hipStream_t st, c
   x.fd_splits = make_fastdiv((uint32_t)g.splits);
   x.fd_nb2 = make_fastdiv((uint32_t)g.nb2);
   const int prec = g.bf16;
+  if (g.ws) return kind == EPI_PLAIN && wgrad_ws_launch(rs, grid, st, g, x);
   if (kind == EPI_PLAIN) return glds_launch_plain(MA, MB, BNT, prec, rs, grid, st, g, x);
   if (kind == EPI_FWD || kind == EPI_BWD) return glds_launch_epi(MA, MB, BNT, prec, kind, grid, st, g, x);
   if (kind == EPI_P0 || kind == EPI_PR || kind == EPI_SMB || kind == EPI_SMBN || kind == EPI_P0_PL)
@@ -303,6 +308,13 @@ ESP_API int esp_set_splitk_mode(int mode) {
   ESP_ARG_CHECK(mode == 0 || mode == 1, "esp_set_splitk_mode: mode must be 0 or 1, got %d", mode);
   const int prev = splitk_mode();
   g_splitk = mode;
+  return prev;
+}
+
+ESP_API int esp_set_wgrad_ws(int mode) {
+  ESP_ARG_CHECK(mode >= 0 && mode <= 2, "esp_set_wgrad_ws: mode must be 0, 1 or 2, got %d", mode);
+  const int prev = g_wgrad_ws;
+  g_wgrad_ws = mode;
   return prev;
 }
 
@@ -669,7 +681,12 @@ static int gemm_run(int mode_a, int mode_b, int M, int N, int K, int batch, int 
       g.bm = 256;
 #endif
   }
-  {
+  auto plan_splits = [&](long want) {  // want: the work units split-K aims for
+    g.splits = 1;
+    g.kchunk = K;
+    g.work = nullptr;
+    g.rs_work = nullptr;
+    g.tickets = nullptr;
     const long tiles = ntiles(g.bnt ? g.bnt : BN, g.bm);
     // each split keeps >= splitk_mink() of K on grids of >= 64 tiles: the reduction launch (~8-10 us)
     // outweighs halving a K = 256 k-loop (the decoder's M = 5248 shapes: 24.8 -> 17.5 and 12.6 us,
@@ -677,8 +694,8 @@ static int gemm_run(int mode_a, int mode_b, int M, int N, int K, int batch, int 
     // gradients over K = 747 / 5248 rows: 8 tiles) needs the splits to fill the chip (19.7 -> 31 us
     // and 21 -> 26 us with 256), so it keeps 128
     const long mink = tiles >= 64 ? splitk_mink() : 128;
-    if (work && tiles < target && K >= 2 * mink) {
-      long sp = (target + tiles - 1) / tiles;
+    if (work && tiles < want && K >= 2 * mink) {
+      long sp = (want + tiles - 1) / tiles;
       const long by_k = K / mink;
       if (sp > by_k) sp = by_k;
       // in-kernel combine (LDS-DMA kernel): partials on whole tiles + tickets in the last 64 KB
@@ -727,7 +744,32 @@ static int gemm_run(int mode_a, int mode_b, int M, int N, int K, int batch, int 
         }
       }
     }
+    return tiles * g.splits;
+  };
+  // The Linear weight gradients (RC x RC, fp32 split products, unbatched, plain epilogue): gemm_wgrad_ws_kernel,
+  // 256 x 128 tiles at one 512-thread block per CU, so split-K aims at one unit per CU.  Taken when K is long
+  // enough that its split-K grid still fills 3/4 of the CUs with units of >= 16 slabs (kWsMinChunk: a unit's
+  // exposed start -- the first slab's global-load latency, its split and the first barrier, about two slab
+  // times -- and its 128 KB partial store stay a small share of its k-loop; the d x d gradients over the decoder's
+  // few thousand tokens keep 128-row tiles: the splits cannot refill the chip there); an unsplit launch without
+  // row sums keeps the specialised plain kinds (EPI_P0 / EPI_PR) of gemm_glds_kernel.
+  constexpr int kWsMinChunk = 16 * GL_BK;
+  bool ws = false;
+  if (ESP_WGRAD_WS && ESP_F32_SPLIT && g_wgrad_ws && mode_a == RC && mode_b == RC && g.bf16 == 0 && prec_in < 0 && batch == 1 &&
+      g.bnt && !cpn && !smb && !band && M % 4 == 0 && N % 4 == 0 && M >= 4 && N >= 4 && K > 0 && !bias && !aux && !act &&
+      !bwd_act && drop_p == 0.f && (g_wgrad_ws == 2 || M >= 256)) {  // (M = 256: the narrowest Linear here)
+    const int bnt0 = g.bnt, bm0 = g.bm;
+    g.bnt = 128;
+    g.bm = WGRAD_WS_BM;
+    const long units = plan_splits(256);
+    ws = (g.splits > 1 || rowsum) && g.wide && !g.tickets && (g_wgrad_ws == 2 || (units >= 192 && g.kchunk >= kWsMinChunk));
+    if (!ws) {
+      g.bnt = bnt0;
+      g.bm = bm0;
+    }
   }
+  g.ws = ws;
+  if (!ws) plan_splits(target);
   hipStream_t st = (hipStream_t)stream;
   const int key = mode_a * 4 + mode_b;
   switch (key) {

@@ -14,10 +14,12 @@
 // Batches: z = z1*nb2 + z2, operand offset = z1*s1 + z2*s2 (two-level strides cover the
 // (batch, head) layouts of attention without copies).
 //
-// Tiling: 128x128 block tile, BK=16, 256 threads = 4 waves (2x2), each wave 64x64 =
-// 2x2 MFMA 32x32 tiles. A lane of half h uses k = 8h+s for MFMA step s (both operands agree);
-// see store_slab/load_frag for the two LDS images. Global->LDS is register-staged and double
-// buffered (next slab's loads are issued before the current slab's MFMAs).
+// Tiling (gemm_glds_kernel): 128x128 block tile (also 128x64, 64x64, 256x128), BK=32 (GL_BK), 256 threads =
+// 4 waves (2x2), each wave 64x64 = 2x2 MFMA 32x32 tiles.  A lane of half h uses k = 16h+s, s = 0..15, of a
+// slab (both operands agree); see Stage / StageS / StageP and frag16 / frag_pl_* for the LDS images.
+// Global->LDS is LDS-DMA (global_load_lds_dwordx4) into a 2-slab ring: the next slab streams in while the
+// current slab's fragments are read.  The Linear weight gradients (RC x RC, fp32) have a kernel of their own
+// with the operand split on dedicated waves: gemm_wgrad_ws.hip.
 // Epilogue (fused): bias, ReLU/Swish (pre-activation optionally stored to `aux`),
 // counter-RNG dropout, alpha scale and beta*R residual.
 #include <stdlib.h>
@@ -47,6 +49,13 @@ constexpr int BM = 128, BN = 128, BK = 32, NT = 256;  // BK: split-K granularity
 #ifndef ESP_GEMM_PIPE
 #define ESP_GEMM_PIPE 1
 #endif
+// 1 (default): the eligible fp32 RC x RC GEMMs (Linear weight gradients) run gemm_wgrad_ws_kernel
+// (gemm_wgrad_ws.hip: split once per block on producer waves); 0: gemm_glds_kernel as before (an A/B build:
+// make VARIANT=_nows EXTRA=-DESP_WGRAD_WS=0)
+#ifndef ESP_WGRAD_WS
+#define ESP_WGRAD_WS 1
+#endif
+constexpr int WGRAD_WS_BM = 256;  // its tile height (x 128 columns)
 
 enum Mode { KC = 0, RC = 1, I2C_KC = 2, I2C_RC = 3, I2CT_KC = 4 };
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SWISH = 2, ACT_MUL = 3 /* bwd_act only: v *= pre */ };
@@ -113,6 +122,7 @@ struct GemmArgs {
              // three bf16 split planes (esp_gemm_f32_bp: B's ld, strides, ps in bf16 elements)
   int bnt;  // LDS-DMA kernel tile width (128, or 64 for narrow / mid-size grids); 0 = fallback kernel
   int bm;   // LDS-DMA kernel tile height: 128, or 64 (with bnt 64) for under-filled grids
+  int ws;   // 1: gemm_wgrad_ws_kernel (bm WGRAD_WS_BM, bnt 128; RC x RC, PREC 0, plain epilogue; one block per CU)
   int bwd_act;       // != 0: backward epilogue  v = drop'(acc) * act'(pre)  (act code, dropout regenerated)
   const float* pre;  // pre-activation (same layout as C) for bwd_act
   float* rowsum;     // != NULL: rowsum[m] += sum_k A(m,k)  (bias gradient of a weight-gradient GEMM)
@@ -1431,7 +1441,8 @@ __device__ __forceinline__ uint32_t i2c_pix_off24(const Im2col& ic, const FastDi
 
 // 16-byte chunk swizzle of a bf16 RC slab's k-row (see StageS)
 __device__ __forceinline__ int bf16_rc_swz(int rowb, int kr) {
-  return rowb == 256 ? (kr & 3) << 2 : ((kr >> 1) & 1) << 2;
+  // (k-rows of 256 or 512 bytes all start on one bank: four k-rows take four 64-byte segments)
+  return rowb >= 256 ? (kr & 3) << 2 : ((kr >> 1) & 1) << 2;
 }
 
 // Per-lane source bookkeeping for one operand: NI wave-instructions per slab.
@@ -2519,6 +2530,8 @@ bool glds_launch_spec(int ma, int mb, int bnt, int prec, int epi, dim3 grid, hip
                       const GldsArgs& x);
 bool glds_launch_pspec(int ma, int mb, int bnt, int prec, int epi, dim3 grid, hipStream_t st, const GemmArgs& g,
                        const GldsArgs& x);
+// gemm_wgrad_ws.hip: the launch of gemm_wgrad_ws_kernel (g.ws; false: not built, ESP_WGRAD_WS=0)
+bool wgrad_ws_launch(bool rs, dim3 grid, hipStream_t st, const GemmArgs& g, const GldsArgs& x);
 // resident blocks per CU of a launch (host side)
 inline int glds_occupancy_rt(int bnt, int epi, int bm, int prec) {
   const int by_regs = bm == 256 ? 1 : bm == 64 ? 4 : (bnt == 64 && (epi == EPI_PLAIN || epi >= EPI_BIAS)) ? 3 : 2;

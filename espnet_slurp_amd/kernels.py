@@ -861,6 +861,17 @@ def set_splitk_mode(mode: int) -> int:
     return prev
 
 
+def set_wgrad_ws(mode: int) -> int:
+    """Kernel of the fp32 weight-gradient GEMMs (esp_set_wgrad_ws): 0 the 128-row LDS-DMA kernel, 1 (default) the
+    warp-specialised kernel where its split-K grid fills the chip, 2 wherever it is eligible.  Returns the
+    previous mode."""
+    lib = _native.load()
+    prev = lib.esp_set_wgrad_ws(int(mode))
+    if prev < 0:
+        raise _native.NativeError(f"esp_set_wgrad_ws failed: {lib.esp_last_error().decode()}")
+    return prev
+
+
 def get_gemm_compute() -> int:
     return _native.load().esp_get_gemm_compute()
 

@@ -72,6 +72,14 @@ int esp_f32_gemm_products(void);
  * tile sums the splits in fixed order; needs the zeroed ticket area of `work`, see above).
  * Initialised from ESP_SPLITK_INKERNEL.  Returns the previous mode. */
 int esp_set_splitk_mode(int mode);
+/* ABI 39.  The kernel of the fp32 RC x RC GEMMs with a plain epilogue (the Linear weight gradients, dW += dy^T x
+ * with the fused bias gradient) of every later esp_gemm_f32 launch (process-wide): 1 (default) = the
+ * warp-specialised kernel (csrc/gemm_wgrad_ws.hip: 256 x 128 tiles, operands split once per block on producer
+ * waves) when M >= 256 and K is long enough for its split-K grid to fill the chip; 2 = that kernel for every
+ * structurally eligible launch (unbatched, M % 4 == N % 4 == 0, LDS-DMA-eligible operands, split K or row sums);
+ * 0 = never (the 128-row LDS-DMA kernel, as in a build with ESP_WGRAD_WS=0, where this call changes nothing).
+ * Unsplit, both kernels give the same C bit for bit.  Returns the previous mode. */
+int esp_set_wgrad_ws(int mode);
 /* esp_gemm_f32 with B also given as its three bf16 split planes (esp_f32_to_planes of the fp32 B,
  * b = hi + mid + lo exactly): the same fp32 split products as esp_gemm_f32 on the fp32 B, in the same
  * order, bit for bit (split-K counts may differ: a different tile width), without splitting B in the
