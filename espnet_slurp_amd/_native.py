@@ -122,6 +122,8 @@ SIGNATURES = {
     "esp_ctc_prefix_init": [P, I, I, I, P, P],
     "esp_ctc_prefix_score": [P, I, I, P, P, I, P, I, I, I, I, P, P, P],
     "esp_ctc_prefix_score_batch": [P, I, I, I, P, P, P, P, I, P, I, I, I, I, P, P, P],
+    "esp_ctc_prefix_extend": [P, I, I, I, P, P, I, I, I, I, P],
+    "esp_cache_gather": [P, P, P, I, I, I, I, I, I, I, I, I, P],
     "esp_decode_attn": [P, L, L, P, L, L, L, P, L, L, L, P, L, L, P, P, I, I, I, I, I, P],
     "esp_decode_attn_masked": [P, L, L, P, L, L, L, P, L, L, L, P, L, L, P, P, P, L, I, I, I, I, I, P],
     "esp_step_linear": [P, L, P, L, P, P, P, F, I, P, L, P, L, I, P, L, I, I, I, I, I, I, P],
@@ -151,7 +153,7 @@ _RESTYPES = {"esp_last_error": ctypes.c_char_p, "esp_abi_version": I, "esp_attn_
              "esp_get_gemm_compute": I, "esp_set_splitk_mode": I, "esp_set_wgrad_ws": I,
              "esp_f32_gemm_products": I}
 _RESTYPES.update({k: L for k in SIGNATURES if k.endswith("_workspace_bytes")})
-ABI_VERSION = 39  # bumped whenever a signature in include/espnet_mi355.h changes
+ABI_VERSION = 40  # bumped whenever a signature in include/espnet_mi355.h changes
 
 _lib = None
 

@@ -80,18 +80,33 @@ class PreparedMemory:
             self._index = (key, K.DecodeIndex(rows, self.hlens[rows], self.kv.device))
         return self._index[1]
 
+    def set_window(self, T: int):
+        """Source attention reads only the first T frames of every utterance from now on (the block-synchronous
+        search's window; kv itself covers all frames, a frame's projection does not depend on the window).  Drops
+        the cached launch index, which holds the lengths."""
+        if not 1 <= T <= self.T:
+            raise ValueError(f"PreparedMemory.set_window: {T} frames outside [1, {self.T}]")
+        self.hlens = np.full(self.U, T, dtype=np.int32)
+        self._index = (None, None)
+
 
 class DecoderCache:
     """Self-attention cache of the one-step decoder: buf (num_blocks, rows, positions, 2D) fp32 holds, for every
     layer, each decode row's prefix keys (columns [0, D)) and values ([D, 2D)) -- not the layer outputs the
     reference caches; the state is opaque to a search, which only passes it back and reorders it.  Preallocated;
     rows and positions grow by doubling; reorder(index) keeps row index[i] as row i (the parent selection
-    after pruning; an index may repeat and may be longer than the current row count)."""
+    after pruning; an index may repeat and may be longer than the current row count).
+
+    reorder_keep(index) is reorder for a search that may take one step back: the rows are gathered into a second
+    buffer (esp_cache_gather, one launch for all layers) and the two buffers swap roles, so the rows of before the
+    selection survive until the next reorder_keep; rollback() goes back to them, one position shorter."""
 
     def __init__(self, num_blocks: int, D: int, device, rows: int = 1, capacity: int = 32):
         self.buf = torch.empty(num_blocks, max(1, rows), max(1, capacity), 2 * D, dtype=torch.float32, device=device)
         self.n = rows   # decode rows in use
         self.len = 0    # positions stored per row
+        self.alt = None   # reorder_keep's second buffer: the rows of before the last reorder_keep
+        self.hist = None  # (n, len) of those rows; None: nothing to go back to
 
     @property
     def row_capacity(self) -> int:
@@ -127,6 +142,32 @@ class DecoderCache:
         if g is not None:
             self.buf[:, :n, :self.len] = g
         self.n = n
+        return self
+
+    def reorder_keep(self, index) -> "DecoderCache":
+        """reorder(index), keeping the rows of before it for one rollback().  Growing this cache afterwards
+        (ensure) allocates a new live buffer and leaves the kept one alone."""
+        index = self._index(index).contiguous()
+        n = int(index.numel())
+        nl, R, C, W = self.buf.shape
+        if self.alt is None or self.alt.shape[1] < n or self.alt.shape[2] < C:
+            while R < n:
+                R *= 2
+            self.alt = torch.empty(nl, R, C, W, dtype=torch.float32, device=self.buf.device)
+        if n and self.len:
+            K.cache_gather(self.buf, self.alt, index, n, self.len, self.n)
+        self.buf, self.alt = self.alt, self.buf
+        self.hist, self.n = (self.n, self.len), n
+        return self
+
+    def rollback(self) -> "DecoderCache":
+        """Back to the rows of before the last reorder_keep, without their newest position: the buffer and the row
+        count of then, len one less (the step that wrote that position is taken again)."""
+        if self.hist is None:
+            raise RuntimeError("DecoderCache.rollback: no reorder_keep to go back from (one step of history is kept)")
+        self.buf, self.alt = self.alt, self.buf
+        self.n, self.len = self.hist[0], self.hist[1] - 1
+        self.hist = None
         return self
 
     def select(self, index) -> "DecoderCache":

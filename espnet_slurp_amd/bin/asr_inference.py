@@ -7,20 +7,28 @@ Tokenizers: "bpe" (sentencepiece model file, as the SLURP recipes use) and "char
 ids2tokens by the model's token_list.  lm= (a TransformerLM, or an ESPnetLanguageModel whose .lm is used) adds
 neural-LM shallow fusion: scorer "lm" with weight lm_weight in the same weighted sum (and so in the "full" pre-beam
 key), as the reference's Speech2Text does with lm_train_config / lm_file / lm_weight (build the LM with
-tasks/lm.build_model and load_state_dict).  Word LM / n-gram / transducer / streaming are out of scope.
+tasks/lm.build_model and load_state_dict).  Word LM / n-gram / transducer / chunk-by-chunk encoding (the encoders'
+forward_infer) are out of scope.
 
 batch_search=True runs the reference Speech2Text's own search instead, BatchBeamSearch (top `beam` over the
 flattened hypothesis x vocabulary scores, <eos> always CTC-scored), on the cached one-step decoder: the
 memory's source-attention K/V are projected once per utterance and every output step computes the newest
 position only.  decode_batch(speeches) encodes several utterances as one padded batch and searches them in
 lockstep (BatchBeamSearch.forward_batch).  The default stays the plain search.
+
+streaming=True is the reference's `--streaming true`: the search is BatchBeamSearchOnlineSim, the block-synchronous
+beam search simulated on the whole utterance's encoder output, with batch_search's scorers and weights.  Its block /
+hop / look-ahead sizes are the encoder's (a contextual block Transformer encoder has all three; the reference reads
+them from the training YAML); with any of them missing or zero they stay unset and the whole utterance is one window.
+No LM and no decode_batch in this mode.
 """
 from typing import List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
-from ..asr.beam_search import BatchBeamSearch, BeamSearch, CTCPrefixScorer, DecoderScorer, Hypothesis, LengthBonus
+from ..asr.beam_search import (BatchBeamSearch, BatchBeamSearchOnlineSim, BeamSearch, CTCPrefixScorer, DecoderScorer,
+                               Hypothesis, LengthBonus)
 
 
 class CharTokenizer:
@@ -45,7 +53,9 @@ class Speech2Text:
     def __init__(self, asr_model, token_list: Optional[List[str]] = None, beam_size: int = 20,
                  ctc_weight: float = 0.5, penalty: float = 0.0, nbest: int = 1, maxlenratio: float = 0.0,
                  minlenratio: float = 0.0, token_type: Optional[str] = None, bpemodel: Optional[str] = None,
-                 batch_search: bool = False, lm=None, lm_weight: float = 1.0):
+                 batch_search: bool = False, lm=None, lm_weight: float = 1.0, streaming: bool = False):
+        if streaming and lm is not None:
+            raise ValueError("Speech2Text: streaming=True does not take an LM (the streaming search has no LM rollback)")
         asr_model.eval()
         self.asr_model = asr_model
         self.device = asr_model.flat.flat.device
@@ -64,6 +74,14 @@ class Speech2Text:
         self.batch_search = batch_search
         self.batch_beam_search = BatchBeamSearch(**kw)  # decode_batch's search, and __call__'s with batch_search
         self.beam_search = self.batch_beam_search if batch_search else BeamSearch(**kw)
+        self.streaming = streaming
+        if streaming:
+            self.beam_search = BatchBeamSearchOnlineSim(**kw)
+            sizes = [getattr(asr_model.encoder, k, None) for k in ("block_size", "hop_size", "look_ahead")]
+            if all(sizes):
+                self.beam_search.set_block_size(sizes[0])
+                self.beam_search.set_hop_size(sizes[1])
+                self.beam_search.set_look_ahead(sizes[2])
         self.maxlenratio, self.minlenratio, self.nbest = maxlenratio, minlenratio, nbest
         if token_type == "bpe":
             self.tokenizer = SentencepiecesTokenizer(bpemodel)
@@ -95,6 +113,8 @@ class Speech2Text:
         The padded-batch encode follows the reference's batch behaviour at utterance ends (the encoder treats a
         shorter utterance's padding as it does in a training batch), so its encoder outputs, and with them the
         scores, are not bit-equal to single-utterance encodes."""
+        if self.streaming:
+            raise ValueError("Speech2Text.decode_batch: the streaming search takes one utterance at a time")
         sp = [torch.as_tensor(s).to(torch.float32) for s in speeches]
         lengths = torch.tensor([s.shape[0] for s in sp], dtype=torch.int64)
         pad = torch.zeros((len(sp), int(lengths.max())) + tuple(sp[0].shape[1:]), dtype=torch.float32)

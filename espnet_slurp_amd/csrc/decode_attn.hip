@@ -172,3 +172,45 @@ ESP_API int esp_decode_attn_masked(const float* q, long ldq, long qoff, const fl
   return decode_attn_launch("esp_decode_attn_masked", q, ldq, qoff, k, ldk, sk, koff, v, ldv, sv, voff, out, ldo, ooff,
                             idx_host, idx_dev, mask, ldm, N, H, dk, nsrc, Tk, stream);
 }
+
+// Row gather of the self-attention K/V cache into a second buffer (DecoderCache.reorder_keep: the parent selection
+// of a beam search that may roll one step back, so the source rows must survive):
+//   dst[l, i, p, :] = src[l, index[i], p, :]   for l < NL, i < n, p < len
+// src (NL, src_R, src_C, W), dst (NL, dst_R, dst_C, W) fp32, W floats per position (K | V), one launch for all
+// layers.  A thread moves one float4; index (device int64) may repeat; an entry outside [0, src_n) is skipped (its
+// destination row is left as it was), so nothing outside the two buffers is touched whatever the index holds.
+namespace {
+__global__ void __launch_bounds__(256)
+cache_gather_kernel(const float* __restrict__ src, float* __restrict__ dst, const long long* __restrict__ index, int NL,
+                    int n, int len, int W4, int src_n, long src_R, long src_C, long dst_R, long dst_C) {
+  const long per_row = (long)len * W4;  // float4s per (layer, row): positions [0, len) are contiguous
+  const long total = (long)NL * n * per_row;
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    const long row = e / per_row, off = e - row * per_row;
+    const int l = (int)(row / n), i = (int)(row - (long)l * n);
+    const long long s = index[i];
+    if (s < 0 || s >= src_n) continue;
+    const float4* sp = reinterpret_cast<const float4*>(src) + ((long)l * src_R + s) * src_C * W4 + off;
+    float4* dp = reinterpret_cast<float4*>(dst) + ((long)l * dst_R + i) * dst_C * W4 + off;
+    *dp = *sp;
+  }
+}
+}  // namespace
+
+ESP_API int esp_cache_gather(const float* src, float* dst, const long long* index, int NL, int n, int len, int W,
+                             int src_n, int src_R, int src_C, int dst_R, int dst_C, void* stream) {
+  ESP_ARG_CHECK(NL >= 1 && n >= 1 && len >= 0 && W >= 4 && !(W & 3) && src_n >= 1 && src_n <= src_R && n <= dst_R &&
+                    len <= src_C && len <= dst_C,
+                "esp_cache_gather: bad sizes NL=%d n=%d len=%d W=%d src %d of %d x %d dst %d x %d", NL, n, len, W, src_n,
+                src_R, src_C, dst_R, dst_C);
+  ESP_ARG_CHECK(src && dst && index && src != dst && !(((uintptr_t)src | (uintptr_t)dst) & 15),
+                "esp_cache_gather: buffers must be distinct, non-null and 16-byte aligned");
+  if (len == 0) return 0;
+  const long total = (long)NL * n * len * (W / 4);
+  const long blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(cache_gather_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
+                     (hipStream_t)stream, src, dst, index, NL, n, len, W / 4, src_n, (long)src_R, (long)src_C,
+                     (long)dst_R, (long)dst_C);
+  ESP_CHECK_LAUNCH("esp_cache_gather");
+  return 0;
+}

@@ -604,3 +604,43 @@ ESP_API int esp_ctc_prefix_score_batch(const float* lp, int U, int Tmax, int V, 
   ESP_CHECK_LAUNCH("esp_ctc_prefix_score_batch");
   return 0;
 }
+
+// Growing CTC prefix states to a longer encoder window (the block-synchronous search,
+// espnet/nets/ctc_prefix_score.py:245-270 CTCPrefixScoreTH.extend_state): a prefix scored on the first t_old frames
+// has emitted all its labels there, so over the new frames [max(t_old, 1), t_new) only its blank path goes on:
+// r[t, 0] = logzero, r[t, 1] = r[t-1, 1] + lp[t, blank].  In place on NH states (NH, Tmax, 2); rows outside the
+// range are not written.  One thread per hypothesis, fp32 adds in frame order (the reference's loop).  Needed
+// because esp_ctc_prefix_score_batch leaves logzero in both columns at and beyond its tlen.
+namespace {
+__global__ void ctc_prefix_extend_kernel(const float* __restrict__ lp_all, int U, int Tmax, int V,
+                                         const int* __restrict__ utt, float* __restrict__ r, int NH, int t0, int t_new,
+                                         int blank) {
+  const int hy = blockIdx.x * blockDim.x + threadIdx.x;
+  if (hy >= NH) return;
+  const int u = utt[hy];
+  if (u < 0 || u >= U) return;
+  const float* lp = lp_all + (long)u * Tmax * V;
+  float* rh = r + (long)hy * Tmax * 2;
+  float acc = rh[2 * (t0 - 1) + 1];
+  for (int t = t0; t < t_new; ++t) {
+    acc = acc + lp[(long)t * V + blank];
+    rh[2 * t] = kLogZero;
+    rh[2 * t + 1] = acc;
+  }
+}
+}  // namespace
+
+ESP_API int esp_ctc_prefix_extend(const float* lp, int U, int Tmax, int V, const int* utt, float* r, int NH, int t_old,
+                                  int t_new, int blank, void* stream) {
+  ESP_ARG_CHECK(U >= 1 && Tmax >= 1 && V >= 1 && NH >= 1 && blank >= 0 && blank < V && t_old >= 0 &&
+                    t_old <= t_new && t_new <= Tmax,
+                "esp_ctc_prefix_extend: bad sizes U=%d Tmax=%d V=%d NH=%d t_old=%d t_new=%d", U, Tmax, V, NH, t_old,
+                t_new);
+  ESP_ARG_CHECK(lp && utt && r, "esp_ctc_prefix_extend: null argument");
+  const int t0 = t_old > 1 ? t_old : 1;
+  if (t0 >= t_new) return 0;
+  hipLaunchKernelGGL(ctc_prefix_extend_kernel, dim3((NH + 63) / 64), dim3(64), 0, (hipStream_t)stream, lp, U, Tmax, V,
+                     utt, r, NH, t0, t_new, blank);
+  ESP_CHECK_LAUNCH("esp_ctc_prefix_extend");
+  return 0;
+}

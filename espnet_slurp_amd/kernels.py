@@ -1514,6 +1514,31 @@ def ctc_prefix_score_batch(lp, tlen_i32, utt_i32, r_prev, last, out_len, cands, 
     return psi, r_new
 
 
+def ctc_prefix_extend(lp, utt_i32, r, t_old, t_new, blank):
+    """Grow the CTC prefix states r (NH, Tmax, 2) in place from a window of t_old frames to t_new: over the frames
+    [max(t_old, 1), t_new) only the blank path goes on (esp_ctc_prefix_extend).  lp (U, Tmax, V), utt_i32 (NH,)
+    device int32."""
+    U, Tmax, V = lp.shape
+    NH = r.shape[0]
+    assert r.shape == (NH, Tmax, 2) and utt_i32.shape == (NH,) and utt_i32.dtype == torch.int32
+    assert lp.is_contiguous() and r.is_contiguous()
+    _f32(lp, r)
+    _native.call("esp_ctc_prefix_extend", _p(lp), U, Tmax, V, _p(utt_i32), _p(r), NH, int(t_old), int(t_new),
+                 int(blank), _st())
+    return r
+
+
+def cache_gather(src, dst, index, n, length, src_n):
+    """dst[l, i, :length] = src[l, index[i], :length] for i < n (esp_cache_gather): src / dst (layers, rows,
+    positions, W) fp32 buffers of a DecoderCache, index n device int64 (entries outside [0, src_n) move nothing)."""
+    NL, src_R, src_C, W = src.shape
+    assert dst.shape[0] == NL and dst.shape[3] == W and src.is_contiguous() and dst.is_contiguous()
+    assert index.dtype == torch.int64 and index.shape == (n,) and index.is_contiguous() and index.device == src.device
+    _f32(src, dst)
+    _native.call("esp_cache_gather", _p(src), _p(dst), _p(index), NL, int(n), int(length), W, int(src_n), src_R, src_C,
+                 dst.shape[1], dst.shape[2], _st())
+
+
 # ----------------------------------------------------------------------------- cached decoder step
 DECODE_ATTN_CHUNK = 64  # keys per online-softmax step of esp_decode_attn (csrc/decode_attn.hip)
 

@@ -531,6 +531,23 @@ int esp_ctc_prefix_score_batch(const float* lp, int U, int Tmax, int V, const in
                                const float* r_prev, const long long* last, int out_len, const long long* cands,
                                int NH, int C, int blank, int eos, float* r_new, float* log_psi, void* stream);
 
+/* ABI 40: growing CTC prefix states to a longer encoder window (the block-synchronous beam search;
+ * espnet/nets/ctc_prefix_score.py:245-270 CTCPrefixScoreTH.extend_state).  r (NH, Tmax, 2) in place: for the frames
+ * t in [max(t_old, 1), t_new), r[h, t, 0] = -1e10 and r[h, t, 1] = r[h, t-1, 1] + lp[utt[h], t, blank] (only the
+ * blank path of an already scored prefix goes on); fp32 adds in frame order, one thread per hypothesis.  Rows
+ * outside that range are not written; a hypothesis whose utterance is out of range is left alone.
+ * 0 <= t_old <= t_new <= Tmax (else status -1); t_old == t_new writes nothing. */
+int esp_ctc_prefix_extend(const float* lp, int U, int Tmax, int V, const int* utt, float* r, int NH, int t_old,
+                          int t_new, int blank, void* stream);
+
+/* ABI 40: row gather of a decoder K/V cache into a second buffer (csrc/decode_attn.hip; DecoderCache.reorder_keep):
+ *   dst[l, i, p, :] = src[l, index[i], p, :]  for l < NL, i < n, p < len
+ * src (NL, src_R, src_C, W) and dst (NL, dst_R, dst_C, W) fp32, distinct and 16-byte aligned, W a multiple of 4;
+ * index: n device int64, may repeat; an entry outside [0, src_n) moves nothing.  src is left as it is, which is what
+ * lets a search take one step back.  n <= dst_R, src_n <= src_R, len <= src_C and dst_C (else status -1). */
+int esp_cache_gather(const float* src, float* dst, const long long* index, int NL, int n, int len, int W, int src_n,
+                     int src_R, int src_C, int dst_R, int dst_C, void* stream);
+
 /* ---- ABI 35: single-query attention of the cached decoder step (csrc/decode_attn.hip; replaces
  * MultiHeadedAttention on a one-row query in TransformerDecoder.forward_one_step,
  * espnet2/asr/decoder/transformer_decoder.py:147-190):
