@@ -137,6 +137,8 @@ SIGNATURES = {
     "esp_cbt_unchunk_fwd": [P, P, I, I, I, I, I, I, I, P],
     "esp_cbt_unchunk_bwd": [P, P, I, I, I, I, I, I, I, P],
     "esp_conv1_dgrad": [P, P, P, I, I, I, I, P],
+    "esp_maskctc_init": [P, I, I, I, ctypes.c_longlong, ctypes.c_double, P, P, P, P, P, P, P],
+    "esp_maskctc_fill": [P, I, I, P, ctypes.c_longlong, I, P],
     # workspace-size queries (host arithmetic; return bytes)
     "esp_grad_norm_workspace_bytes": [L],
     "esp_layernorm_bwd_workspace_bytes": [I, I],
@@ -153,7 +155,7 @@ _RESTYPES = {"esp_last_error": ctypes.c_char_p, "esp_abi_version": I, "esp_attn_
              "esp_get_gemm_compute": I, "esp_set_splitk_mode": I, "esp_set_wgrad_ws": I,
              "esp_f32_gemm_products": I}
 _RESTYPES.update({k: L for k in SIGNATURES if k.endswith("_workspace_bytes")})
-ABI_VERSION = 40  # bumped whenever a signature in include/espnet_mi355.h changes
+ABI_VERSION = 41  # bumped whenever a signature in include/espnet_mi355.h changes
 
 _lib = None
 

@@ -44,11 +44,12 @@ class DecoderLayer(nn.Module):
         self.norm2 = LayerNorm(size)
         self.norm3 = LayerNorm(size)
         self.p = dropout_rate
+        self.causal = True  # self-attention mask j <= i; False (MLMDecoder): every valid key
 
     def fwd(self, x, mem, B, L, Tm, tgt_klen, mem_klen, seeds, training):
         c = Ctx()
         h, c.ln1 = self.norm1.fwd(x, gemm_only=True)
-        x, c.sa = self.self_attn.fwd(h, x, B, L, tgt_klen, True, self.p, seeds, training)
+        x, c.sa = self.self_attn.fwd(h, x, B, L, tgt_klen, self.causal, self.p, seeds, training)
         h, c.ln2 = self.norm2.fwd(x, gemm_only=True)
         x, c.src = self.src_attn.fwd(h, x, B, L, mem_klen, False, self.p, seeds, training, mem=mem, Tk=Tm)
         h, c.ln3 = self.norm3.fwd(x, gemm_only=True)

@@ -89,6 +89,8 @@ class Prepared(dict):
 
 
 class ESPnetASRModel(AbsESPnetModel):
+    target_draw_args: Tuple[str, ...] = ()  # forward() keyword arguments handed to prepare() as target_draws
+
     def __init__(self, vocab_size: int, token_list: Union[Tuple[str, ...], List[str]], frontend, specaug,
                  normalize, preencoder, encoder, postencoder, decoder, ctc, joint_network=None,
                  ctc_weight: float = 0.5, interctc_weight: float = 0.0, ignore_id: int = -1,
@@ -246,7 +248,7 @@ class ESPnetASRModel(AbsESPnetModel):
     # ------------------------------------------------------------------ forward
     def prepare(self, speech_lengths: torch.Tensor, text: torch.Tensor, text_lengths: torch.Tensor, T_in: int,
                 F_in: int, specaug_draws: Optional[dict] = None, t_bucket: Optional[int] = None,
-                u_bucket: Optional[int] = None) -> Prepared:
+                u_bucket: Optional[int] = None, **target_draws) -> Prepared:
         """All host-side work of a step (espnet_model.py:169-297 before any kernel): lengths,
         the target slice, add_sos_eos, SpecAug draws (CPU generator, as time_warp.py), the
         dropout seeds.  Returns host tensors; `.to_device()` moves them (pinned, async).
@@ -256,7 +258,9 @@ class ESPnetASRModel(AbsESPnetModel):
         ys_out with ignore_id: one decoder row more per token of padding, all ignored).  Every
         length-derived quantity (SpecAug draws, encoder lengths, the valid frame count
         `tvalid` the convolution module bounds itself with) is still taken from this batch's
-        own padded length, so the step computes what the reference computes on it."""
+        own padded length, so the step computes what the reference computes on it.
+
+        target_draws: explicit random draws of _decoder_targets (none here: add_sos_eos draws nothing)."""
         assert text_lengths.dim() == 1, text_lengths.shape
         B = int(speech_lengths.shape[0])
         text = text.detach().cpu().clone()
@@ -302,15 +306,21 @@ class ESPnetASRModel(AbsESPnetModel):
             host["ys"] = text_cpu
             host["tlens"] = tl_cpu.to(torch.int32)
         if self.decoder is not None:
-            ys_in, ys_out, ys_in_lens = add_sos_eos(text_cpu, tl_cpu, self.sos, self.eos, self.ignore_id)
-            if u_bucket is not None and ys_in.shape[1] < int(u_bucket) + 1:
-                extra = int(u_bucket) + 1 - ys_in.shape[1]
-                ys_in = torch.cat([ys_in, torch.full((B, extra), self.eos, dtype=ys_in.dtype)], 1)
-                ys_out = torch.cat([ys_out, torch.full((B, extra), self.ignore_id, dtype=ys_out.dtype)], 1)
+            ys_in, ys_out, ys_in_lens = self._decoder_targets(text_cpu, tl_cpu, u_bucket, **target_draws)
             prep["L"] = int(ys_in.shape[1])
             host["ys_in"], host["ys_out"] = ys_in, ys_out
             host["ys_in_lens"] = ys_in_lens.to(torch.int32)
         return prep
+
+    def _decoder_targets(self, text_cpu: torch.Tensor, tl_cpu: torch.Tensor, u_bucket: Optional[int]):
+        """The decoder's (ys_in, ys_out, ys_in_lens) of a batch, on the host: add_sos_eos, padded to u_bucket + 1
+        columns when the target axis is bucketed.  A subclass with other decoder targets overrides this."""
+        ys_in, ys_out, ys_in_lens = add_sos_eos(text_cpu, tl_cpu, self.sos, self.eos, self.ignore_id)
+        if u_bucket is not None and ys_in.shape[1] < int(u_bucket) + 1:
+            B, extra = ys_in.shape[0], int(u_bucket) + 1 - ys_in.shape[1]
+            ys_in = torch.cat([ys_in, torch.full((B, extra), self.eos, dtype=ys_in.dtype)], 1)
+            ys_out = torch.cat([ys_out, torch.full((B, extra), self.ignore_id, dtype=ys_out.dtype)], 1)
+        return ys_in, ys_out, ys_in_lens
 
     def _features(self, speech: torch.Tensor, prep: Prepared) -> torch.Tensor:
         """frontend -> SpecAug (training) -> normalize, from the prepared batch's device tensors."""
@@ -414,7 +424,8 @@ class ESPnetASRModel(AbsESPnetModel):
             self.flat.ensure_grads()  # after a torch optimizer's zero_grad(set_to_none=True)
         text[text == -1] = self.ignore_id  # the reference mutates the batch (espnet_model.py:196)
         F_in = speech.shape[2] if speech.dim() == 3 else 0
-        prep = self.prepare(speech_lengths, text, text_lengths, speech.shape[1], F_in, specaug_draws)
+        prep = self.prepare(speech_lengths, text, text_lengths, speech.shape[1], F_in, specaug_draws,
+                            **{k: kwargs[k] for k in self.target_draw_args if k in kwargs})
         prep.to_device(speech.device)
         return self.forward_prepared(speech, prep)
 

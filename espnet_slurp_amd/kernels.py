@@ -1581,6 +1581,40 @@ def decode_attn_masked(q, ldq, qoff, k, ldk, sk, koff, v, ldv, sv, voff, out, ld
                  ooff, index.host.ctypes.data, _p(index.dev), _p(mask), ldm, index.n, H, dk, nsrc, Tk, _st())
 
 
+# ----------------------------------------------------------------------------- Mask-CTC mask-predict
+MASKCTC_FILL_MAX_L = 2048  # positions esp_maskctc_fill ranks in LDS (csrc/maskctc.hip)
+
+
+def maskctc_init(lp, mask_token, threshold, blank=0):
+    """Greedy CTC of one utterance -> the masked decoder input (esp_maskctc_init): lp (T, V) fp32 log-softmax.
+    Returns (y_in (T,) int64, tok_logp (T,), tok_prob (T,), counts (2,) int32 = {L, mask_num}), all on the device;
+    the first L entries of the three arrays are valid.  No host synchronisation."""
+    T, V = lp.shape
+    _f32(lp)
+    assert lp.is_contiguous()
+    dev = lp.device
+    fid = torch.empty(T, dtype=torch.int32, device=dev)
+    flp = torch.empty(T, dtype=torch.float32, device=dev)
+    y_in = torch.empty(T, dtype=torch.int64, device=dev)
+    tok_logp = torch.empty(T, dtype=torch.float32, device=dev)
+    tok_prob = torch.empty(T, dtype=torch.float32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    _native.call("esp_maskctc_init", _p(lp), T, V, int(blank), int(mask_token), float(threshold), _p(fid), _p(flp),
+                 _p(y_in), _p(tok_logp), _p(tok_prob), _p(counts), _st())
+    return y_in, tok_logp, tok_prob, counts
+
+
+def maskctc_fill(logits, y_in, mask_token, k):
+    """One mask-predict step in place (esp_maskctc_fill): logits (L, V + 1) fp32 raw decoder outputs, y_in (>= L,)
+    int64 on the device.  k > 0: the k masked positions with the largest row maxima take their argmax; k == 0:
+    every masked position does."""
+    L, V1 = logits.shape
+    _f32(logits)
+    assert logits.is_contiguous() and y_in.dtype == torch.int64 and y_in.is_contiguous() and y_in.numel() >= L
+    assert y_in.device == logits.device
+    _native.call("esp_maskctc_fill", _p(logits), L, V1, _p(y_in), int(mask_token), int(k), _st())
+
+
 # ----------------------------------------------------------------------------- Transformer LM step
 LM_STEP_FUSED = True   # the LM step's linears on esp_step_linear (5 launches per layer); False: generic kernels
 LM_STEP_MAX_ROWS = 512  # rows up to which the fused step is used (measured: DESIGN 3.6b); above: the generic kernels

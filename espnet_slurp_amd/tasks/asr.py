@@ -10,12 +10,14 @@ from typing import Dict, Optional, Type
 import torch
 
 from ..asr.ctc import CTC
+from ..asr.decoder.mlm_decoder import MLMDecoder
 from ..asr.decoder.transformer_decoder import TransformerDecoder
 from ..asr.encoder.branchformer_encoder import BranchformerEncoder
 from ..asr.encoder.conformer_encoder import ConformerEncoder
 from ..asr.encoder.contextual_block_transformer_encoder import ContextualBlockTransformerEncoder
 from ..asr.encoder.transformer_encoder import TransformerEncoder
 from ..asr.espnet_model import ESPnetASRModel
+from ..asr.maskctc_model import MaskCTCModel
 from ..asr.specaug.specaug import SpecAug
 from ..asr.frontend.default import DefaultFrontend
 from ..layers.global_mvn import GlobalMVN
@@ -49,12 +51,13 @@ frontend_choices = ClassChoices("frontend", dict(default=DefaultFrontend), defau
 specaug_choices = ClassChoices("specaug", dict(specaug=SpecAug), default=None, optional=True)
 normalize_choices = ClassChoices("normalize", dict(global_mvn=GlobalMVN, utterance_mvn=UtteranceMVN),
                                  default="utterance_mvn", optional=True)
-model_choices = ClassChoices("model", dict(espnet=ESPnetASRModel), default="espnet")
+model_choices = ClassChoices("model", dict(espnet=ESPnetASRModel, maskctc=MaskCTCModel), default="espnet")
 encoder_choices = ClassChoices("encoder", dict(conformer=ConformerEncoder, transformer=TransformerEncoder,
                                                branchformer=BranchformerEncoder,
                                                contextual_block_transformer=ContextualBlockTransformerEncoder),
                            default="rnn")
-decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder), default="rnn", optional=True)
+decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder, mlm=MLMDecoder), default="rnn",
+                               optional=True)
 
 
 def build_model(args: argparse.Namespace, device="cuda") -> ESPnetASRModel:

@@ -632,6 +632,27 @@ int esp_cbt_unchunk_fwd(const float* xs, float* y, int B, int T, int D, int bs, 
 int esp_cbt_unchunk_bwd(const float* dy, float* dxs, int B, int T, int D, int bs, int hop, int la, int nblk,
                         void* stream);
 
+/* ---- ABI 41: Mask-CTC mask-predict decoding (csrc/maskctc.hip; espnet2/asr/maskctc_model.py
+ * MaskCTCInference.forward).  One workgroup per utterance; selection only (max, argmax, rank).
+ *
+ * esp_maskctc_init (:288-317): lp (T, V) fp32, the CTC log-softmax of one utterance.  Per frame the maximum and its
+ * first index; runs of equal ids are collapsed, blank runs dropped, and each remaining run (token) takes the maximum
+ * log-probability of its frames: tok_logp[i], bit-equal to that fp32 maximum, tok_prob[i] = expf(tok_logp[i]).  Token
+ * i is masked when (double)tok_prob[i] < threshold (the reference compares a Python float holding the fp32 value):
+ * y_in[i] = mask_token, else the token id.  counts = {L, mask_num}: tokens and masked tokens.  y_in (int64),
+ * tok_logp, tok_prob: T entries each, the first L written.  fid (int32) / flp (fp32): T entries of scratch (the
+ * per-frame argmax and maximum).  exp is monotone, so the per-frame argmax of lp is the reference's argmax of
+ * exp(lp) unless two distinct log-probabilities round to one probability.
+ *
+ * esp_maskctc_fill (:327-331, :336-337): logits (L, V1) fp32 raw decoder outputs, V1 = vocabulary + <mask>; y_in
+ * (L) int64 in place.  Every position holding mask_token takes the maximum and first argmax of its row over all V1
+ * classes (the mask token included, as the reference).  k > 0: the k masked positions with the largest maxima are
+ * set to their argmax (rank by counting, the lower index first on equal maxima); k == 0: every masked position is.
+ * 1 <= L <= 2048 (else status -1). */
+int esp_maskctc_init(const float* lp, int T, int V, int blank, long long mask_token, double threshold, int* fid,
+                     float* flp, long long* y_in, float* tok_logp, float* tok_prob, int* counts, void* stream);
+int esp_maskctc_fill(const float* logits, int L, int V1, long long* y_in, long long mask_token, int k, void* stream);
+
 /* esp_conv1_dgrad (csrc/conv.hip): the feature gradient of the subsampling's first convolution (3 x 3, stride 2),
  * dx (B, T, F) = the adjoint of conv1 applied to dz1 (B, T1, F1, D) (ReLU mask already applied), W (D, 9).  Training
  * does not call it (the features are data); an encoder's run_backward forms it on request. */
