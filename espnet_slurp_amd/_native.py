@@ -137,6 +137,10 @@ SIGNATURES = {
     "esp_cbt_unchunk_fwd": [P, P, I, I, I, I, I, I, I, P],
     "esp_cbt_unchunk_bwd": [P, P, I, I, I, I, I, I, I, P],
     "esp_conv1_dgrad": [P, P, P, I, I, I, I, P],
+    "esp_causal_attn_fwd": [P, P, P, P, I, I, I, I, P],
+    "esp_causal_attn_bwd": [P, P, P, P, P, I, I, I, I, P],
+    "esp_lm_front_fwd": [P, P, P, F, F, P, I, I, F, U64, F, U64, P, P, P, I, I, P],
+    "esp_lm_front_bwd": [P, P, P, P, P, P, F, I, F, U64, F, U64, P, P, P, P, I, I, P, L, P],
     "esp_maskctc_init": [P, I, I, I, ctypes.c_longlong, ctypes.c_double, P, P, P, P, P, P, P],
     "esp_maskctc_fill": [P, I, I, P, ctypes.c_longlong, I, P],
     # workspace-size queries (host arithmetic; return bytes)
@@ -155,7 +159,7 @@ _RESTYPES = {"esp_last_error": ctypes.c_char_p, "esp_abi_version": I, "esp_attn_
              "esp_get_gemm_compute": I, "esp_set_splitk_mode": I, "esp_set_wgrad_ws": I,
              "esp_f32_gemm_products": I}
 _RESTYPES.update({k: L for k in SIGNATURES if k.endswith("_workspace_bytes")})
-ABI_VERSION = 41  # bumped whenever a signature in include/espnet_mi355.h changes
+ABI_VERSION = 42  # bumped whenever a signature in include/espnet_mi355.h changes
 
 _lib = None
 

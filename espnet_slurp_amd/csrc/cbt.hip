@@ -8,6 +8,7 @@
 // esp_block_attn_fwd / _bwd: self-attention over Z independent sequences of S <= 64 slots, one workgroup per
 // (sequence, head).  Q, K and V (S x dk each) are staged once in LDS; the scores, the fixed mask (key j valid iff
 // j <= S - 2, query row 0 dead: its output is zero), the softmax, the dropout and P.V stay in registers and LDS.
+// The tile helpers live in attn_tile.h (shared with causal_attn.hip):
 //   threads  = 256, thread (ti, tj) = (tid / 16, tid % 16) owns score rows ti + 16a and columns tj + 16b
 //              (a, b < NA = ceil(S / 16)): a 16-lane row group reduces a score row with four xor shuffles.
 //   LDS      = row-major tiles of pitch dk + 4 (S x S tiles: 16 NA + 4) floats.  The pitch / 4 is odd, so the 16
@@ -20,147 +21,15 @@
 //
 // esp_cbt_chunk_fwd / _bwd, esp_cbt_ctx_shift_fwd / _bwd, esp_cbt_unchunk_fwd / _bwd: the block layout around the
 // layers (see include/espnet_mi355.h); all backward passes are gathers.
-#include "common.h"
+#include "attn_tile.h"  // stage_tile, mm_nt / mm_nn / mm_tn, group_max / group_sum, store_rows, region_a, grant_lds
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kMaxS = 64;
-
-template <int DK>
-__device__ __forceinline__ void stage_tile(float* __restrict__ dst, const float* __restrict__ src, long ld, int S,
-                                           int SP) {
-  constexpr int P = DK + 4, C4 = DK / 4;
-  for (int i = threadIdx.x; i < SP * C4; i += kThreads) {
-    const int r = i / C4, c = i - r * C4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < S) v = *reinterpret_cast<const float4*>(src + (long)r * ld + 4 * c);
-    *reinterpret_cast<float4*>(dst + r * P + 4 * c) = v;
-  }
-}
-
-// acc[a][b] = sum_k A[ti + 16a][k] * B[tj + 16b][k], both tiles of pitch DK + 4
-template <int DK, int NA>
-__device__ __forceinline__ void mm_nt(const float* __restrict__ A, const float* __restrict__ B, int ti, int tj,
-                                      float (&acc)[NA][NA]) {
-  constexpr int P = DK + 4;
-#pragma unroll
-  for (int a = 0; a < NA; ++a)
-#pragma unroll
-    for (int b = 0; b < NA; ++b) acc[a][b] = 0.f;
-#pragma unroll 2
-  for (int k = 0; k < DK; k += 4) {
-    float4 av[NA], bv[NA];
-#pragma unroll
-    for (int a = 0; a < NA; ++a) av[a] = *reinterpret_cast<const float4*>(A + (ti + 16 * a) * P + k);
-#pragma unroll
-    for (int b = 0; b < NA; ++b) bv[b] = *reinterpret_cast<const float4*>(B + (tj + 16 * b) * P + k);
-#pragma unroll
-    for (int a = 0; a < NA; ++a)
-#pragma unroll
-      for (int b = 0; b < NA; ++b) {
-        float s = acc[a][b];
-        s = fmaf(av[a].x, bv[b].x, s);
-        s = fmaf(av[a].y, bv[b].y, s);
-        s = fmaf(av[a].z, bv[b].z, s);
-        s = fmaf(av[a].w, bv[b].w, s);
-        acc[a][b] = s;
-      }
-  }
-}
-
-// acc[a][c] = sum_{j < nk} X[ti + 16a][j] * B[j][tj*CW + c]   (X of pitch PX, B of pitch DK + 4; nk % 4 == 0)
-template <int DK, int NA>
-__device__ __forceinline__ void mm_nn(const float* __restrict__ X, int PX, const float* __restrict__ B, int nk,
-                                      int ti, int tj, float (&acc)[NA][DK / 16]) {
-  constexpr int P = DK + 4, CW = DK / 16;
-#pragma unroll
-  for (int a = 0; a < NA; ++a)
-#pragma unroll
-    for (int c = 0; c < CW; ++c) acc[a][c] = 0.f;
-  for (int j = 0; j < nk; j += 4) {
-    float xv[NA][4];
-#pragma unroll
-    for (int a = 0; a < NA; ++a) {
-      const float4 t = *reinterpret_cast<const float4*>(X + (ti + 16 * a) * PX + j);
-      xv[a][0] = t.x, xv[a][1] = t.y, xv[a][2] = t.z, xv[a][3] = t.w;
-    }
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      float bv[CW];
-#pragma unroll
-      for (int c = 0; c < CW; ++c) bv[c] = B[(j + jj) * P + tj * CW + c];
-#pragma unroll
-      for (int a = 0; a < NA; ++a)
-#pragma unroll
-        for (int c = 0; c < CW; ++c) acc[a][c] = fmaf(xv[a][jj], bv[c], acc[a][c]);
-    }
-  }
-}
-
-// acc[a][c] = sum_{i < ni} X[i][ti + 16a] * B[i][tj*CW + c]
-template <int DK, int NA>
-__device__ __forceinline__ void mm_tn(const float* __restrict__ X, int PX, const float* __restrict__ B, int ni,
-                                      int ti, int tj, float (&acc)[NA][DK / 16]) {
-  constexpr int P = DK + 4, CW = DK / 16;
-#pragma unroll
-  for (int a = 0; a < NA; ++a)
-#pragma unroll
-    for (int c = 0; c < CW; ++c) acc[a][c] = 0.f;
-#pragma unroll 2
-  for (int i = 0; i < ni; ++i) {
-    float xv[NA], bv[CW];
-#pragma unroll
-    for (int a = 0; a < NA; ++a) xv[a] = X[i * PX + ti + 16 * a];
-#pragma unroll
-    for (int c = 0; c < CW; ++c) bv[c] = B[i * P + tj * CW + c];
-#pragma unroll
-    for (int a = 0; a < NA; ++a)
-#pragma unroll
-      for (int c = 0; c < CW; ++c) acc[a][c] = fmaf(xv[a], bv[c], acc[a][c]);
-  }
-}
-
-// reductions over the 16 lanes of a row group (lanes 16 ti .. 16 ti + 15 of the wave)
-__device__ __forceinline__ float group_max(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// rows i = ti + 16a (< S) of an S x DK result -> global rows of pitch ld
-template <int DK, int NA>
-__device__ __forceinline__ void store_rows(float* __restrict__ dst, long ld, int S, int ti, int tj,
-                                           const float (&acc)[NA][DK / 16]) {
-  constexpr int CW = DK / 16;
-#pragma unroll
-  for (int a = 0; a < NA; ++a) {
-    const int i = ti + 16 * a;
-    if (i >= S) continue;
-    float* p = dst + (long)i * ld + tj * CW;
-    if constexpr (CW == 4) {
-      *reinterpret_cast<float4*>(p) = make_float4(acc[a][0], acc[a][1], acc[a][2], acc[a][3]);
-    } else if constexpr (CW == 2) {
-      *reinterpret_cast<float2*>(p) = make_float2(acc[a][0], acc[a][1]);
-    } else {
-      p[0] = acc[a][0];
-    }
-  }
-}
 
 __device__ __forceinline__ float drop_mul(uint64_t seed, uint32_t thresh, float dscale, long zh, int i, int j) {
   if (!thresh) return 1.f;
   return esp::keep_elem(seed, (uint64_t)((zh * kMaxS + i) * kMaxS + j), thresh) ? dscale : 0.f;
-}
-
-template <int DK, int NA>
-constexpr int region_a() {  // floats of a tile that holds an SP x DK operand first and an SP x SP matrix later
-  return 16 * NA * ((DK + 4) > (16 * NA + 4) ? (DK + 4) : (16 * NA + 4));
 }
 
 template <int DK, int NA>
@@ -298,14 +167,6 @@ template <int DK, int NA>
 size_t fwd_lds() { return sizeof(float) * (region_a<DK, NA>() + 2 * 16 * NA * (DK + 4)); }
 template <int DK, int NA>
 size_t bwd_lds() { return sizeof(float) * (region_a<DK, NA>() + 3 * 16 * NA * (DK + 4)); }
-
-// dynamic LDS above 64 KiB (the backward at S > 48, dk = 64: 68 KiB of the CU's 160) has to be granted per kernel
-template <typename Kern>
-hipError_t grant_lds(Kern kern, size_t bytes) {
-  if (bytes <= 65536) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)bytes);
-}
 
 template <int DK, int NA>
 int launch_fwd(const float* qkv, float* ctx, float* lse, long Z, int S, int H, float p, uint64_t seed,

@@ -24,6 +24,13 @@
 //
 // esp_step_ln_act: y[r, :] = relu(LN(x[r, :])) * xscale + pe[pos0 + r % L, :] -- the tail of the LM's input layer
 // (Linear -> torch.nn.LayerNorm -> ReLU -> positional step; pe NULL: the identity positional step).  A wave per row.
+//
+// esp_lm_front_fwd / _bwd: the same tail in training form (espnet1 encoder.py input_layer "linear": LayerNorm ->
+// Dropout -> ReLU -> pos_enc_class, whose PositionalEncoding ends in a second Dropout): y = drop2(relu(drop1(LN(x)))
+// * xscale + pe[r % L]); pe NULL: y = relu(drop1(LN(x))).  The masks come from the counter RNG by element index
+// r*D + c, so they do not depend on the launch geometry and the backward regenerates them from the same seeds; the
+// forward saves the row mean / rstd, the backward recomputes the ReLU decision from them and hands the gradient of
+// LN(x) to esp_layernorm_bwd.  At p1 = 0 the forward's values are esp_step_ln_act's bit for bit.
 #include "common.h"
 
 namespace {
@@ -149,6 +156,77 @@ step_ln_act_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
   }
 }
 
+// the front's pre-activation t = drop1(LN(x)) of one element; relu(t) > 0 iff the element is kept and LN(x) > 0
+__device__ __forceinline__ float front_pre(float x, float mean, float rstd, float gamma, float beta, uint64_t seed1,
+                                           uint32_t th1, float ds1, uint64_t idx) {
+  float t = fmaf((x - mean) * rstd, gamma, beta);
+  if (th1) t = esp::keep_elem(seed1, idx, th1) ? t * ds1 : 0.f;
+  return t;
+}
+
+// step_ln_act_kernel's arithmetic with the two dropouts of the training form and the saved row statistics
+__global__ void __launch_bounds__(256)
+lm_front_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                    float eps, float xscale, const float* __restrict__ pe, int L, float* __restrict__ y,
+                    float* __restrict__ mean_out, float* __restrict__ rstd_out, int rows, int D, uint64_t seed1,
+                    uint64_t seed2, const uint64_t* __restrict__ key, uint32_t th1, float ds1, uint32_t th2,
+                    float ds2) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;  // wave-uniform
+  seed1 = esp::keyed(seed1, key);
+  seed2 = esp::keyed(seed2, key);
+  const float* xr = x + r * D;
+  float s = 0.f;
+  for (int c = lane; c < D; c += 64) s += xr[c];
+  const float mean = esp::wave_sum(s) / (float)D;
+  float q = 0.f;
+  for (int c = lane; c < D; c += 64) {
+    const float d = xr[c] - mean;
+    q = fmaf(d, d, q);
+  }
+  const float rstd = 1.0f / sqrtf(esp::wave_sum(q) / (float)D + eps);
+  if (lane == 0) {
+    mean_out[r] = mean;
+    rstd_out[r] = rstd;
+  }
+  const float* per = pe ? pe + (long)(r % L) * D : nullptr;
+  for (int c = lane; c < D; c += 64) {
+    const uint64_t idx = (uint64_t)(r * D + c);
+    float v = fmaxf(front_pre(xr[c], mean, rstd, gamma[c], beta[c], seed1, th1, ds1, idx), 0.f);
+    if (per) {
+      v = fmaf(v, xscale, per[c]);
+      if (th2) v = esp::keep_elem(seed2, idx, th2) ? v * ds2 : 0.f;
+    }
+    y[r * D + c] = v;
+  }
+}
+
+// dz = gradient with respect to LN(x): the second dropout, the scale, the ReLU decision recomputed from the saved
+// statistics, the first dropout; esp_layernorm_bwd takes it from there
+__global__ void __launch_bounds__(256)
+lm_front_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ gamma,
+                    const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd,
+                    float xscale, int has_pe, float* __restrict__ dz, int rows, int D, uint64_t seed1, uint64_t seed2,
+                    const uint64_t* __restrict__ key, uint32_t th1, float ds1, uint32_t th2, float ds2) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;  // wave-uniform
+  seed1 = esp::keyed(seed1, key);
+  seed2 = esp::keyed(seed2, key);
+  const float m = mean[r], rs = rstd[r];
+  for (int c = lane; c < D; c += 64) {
+    const uint64_t idx = (uint64_t)(r * D + c);
+    float g = dy[r * D + c];
+    if (has_pe) {
+      if (th2) g = esp::keep_elem(seed2, idx, th2) ? g * ds2 : 0.f;
+      g *= xscale;
+    }
+    const float t = front_pre(x[r * D + c], m, rs, gamma[c], beta[c], seed1, th1, ds1, idx);
+    dz[r * D + c] = t > 0.f ? g * ds1 : 0.f;
+  }
+}
+
 }  // namespace
 
 ESP_API int esp_step_linear(const float* x, long ldx, const float* W, long ldw, const float* bias,
@@ -191,4 +269,43 @@ ESP_API int esp_step_ln_act(const float* x, const float* gamma, const float* bet
                      beta, eps, xscale, pe, L, pos0, y, rows, D);
   ESP_CHECK_LAUNCH("esp_step_ln_act");
   return 0;
+}
+
+ESP_API int esp_lm_front_fwd(const float* x, const float* gamma, const float* beta, float eps, float xscale,
+                             const float* pe, int L, int pe_rows, float p1, unsigned long long seed1, float p2,
+                             unsigned long long seed2, float* y, float* mean, float* rstd, int rows, int D,
+                             void* stream) {
+  ESP_ARG_CHECK(x && gamma && beta && y && mean && rstd && rows >= 1 && D >= 1 && L >= 1,
+                "esp_lm_front_fwd: bad arguments rows=%d D=%d L=%d", rows, D, L);
+  ESP_ARG_CHECK(!pe || (rows < L ? rows : L) <= pe_rows, "esp_lm_front_fwd: %d positions outside a table of %d rows",
+                rows < L ? rows : L, pe_rows);
+  ESP_ARG_CHECK(p1 >= 0.f && p1 < 1.f && p2 >= 0.f && p2 < 1.f, "esp_lm_front_fwd: dropout %f / %f outside [0, 1)", p1,
+                p2);
+  const uint32_t th1 = esp::drop_threshold(p1), th2 = pe ? esp::drop_threshold(p2) : 0;
+  hipLaunchKernelGGL(lm_front_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, gamma,
+                     beta, eps, xscale, pe, L, y, mean, rstd, rows, D, (uint64_t)seed1, (uint64_t)seed2,
+                     esp::rng_key_ptr(), th1, esp::drop_scale(th1), th2, esp::drop_scale(th2));
+  ESP_CHECK_LAUNCH("esp_lm_front_fwd");
+  return 0;
+}
+
+ESP_API int esp_lm_front_bwd(const float* dy, const float* x, const float* gamma, const float* beta, const float* mean,
+                             const float* rstd, float xscale, int has_pe, float p1, unsigned long long seed1, float p2,
+                             unsigned long long seed2, float* dz, float* dx, float* dgamma, float* dbeta, int rows,
+                             int D, float* work, long work_bytes, void* stream) {
+  ESP_ARG_CHECK(dy && x && gamma && beta && mean && rstd && dz && dx && dgamma && dbeta && rows >= 1 && D >= 1,
+                "esp_lm_front_bwd: bad arguments rows=%d D=%d", rows, D);
+  ESP_ARG_CHECK(dz != dy && dz != dx, "esp_lm_front_bwd: dz must be a buffer of its own");
+  ESP_ARG_CHECK(p1 >= 0.f && p1 < 1.f && p2 >= 0.f && p2 < 1.f, "esp_lm_front_bwd: dropout %f / %f outside [0, 1)", p1,
+                p2);
+  ESP_ARG_CHECK(D % 4 == 0 && work_bytes >= esp_layernorm_bwd_workspace_bytes(rows, D),
+                "esp_lm_front_bwd: D=%d must be a multiple of 4 and the workspace (%ld B) esp_layernorm_bwd's", D,
+                work_bytes);
+  const uint32_t th1 = esp::drop_threshold(p1), th2 = has_pe ? esp::drop_threshold(p2) : 0;
+  hipLaunchKernelGGL(lm_front_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dy, x,
+                     gamma, beta, mean, rstd, xscale, has_pe, dz, rows, D, (uint64_t)seed1, (uint64_t)seed2,
+                     esp::rng_key_ptr(), th1, esp::drop_scale(th1), th2, esp::drop_scale(th2));
+  ESP_CHECK_LAUNCH("esp_lm_front_bwd");
+  // dx = LN'(dz), dgamma / dbeta += (the LayerNorm adjoint every other norm of the model uses)
+  return esp_layernorm_bwd(dz, x, gamma, mean, rstd, dx, 0, dgamma, dbeta, rows, D, work, work_bytes, stream);
 }

@@ -1684,6 +1684,78 @@ def step_ln_act(x, gamma, beta, eps, y, *, pe=None, xscale=1.0, L=1, pos0=0):
     return y
 
 
+# ----------------------------------------------------------------------------- Transformer LM training
+# The LM layers' causal self-attention on esp_causal_attn_fwd / _bwd (one fused kernel each way, no score tensor);
+# False, or a shape outside the fused kernel's limits: MultiHeadedAttention's generic kernels (the in-repo baseline
+# of tools/bench_lm_train.py)
+LM_ATTN_FUSED = True
+CAUSAL_ATTN_MAX_L = {16: 64, 32: 64, 64: 64, 128: 64}  # esp_causal_attn_*: Lmax per d_k
+
+
+def causal_attn_ok(L: int, dk: int) -> bool:
+    return dk in CAUSAL_ATTN_MAX_L and 1 <= L <= CAUSAL_ATTN_MAX_L[dk]
+
+
+def causal_attn_fwd(qkv, klen_i32, ctx, lse, B, L, H, dk):
+    """ctx (B*L, H*dk) = causal softmax-attention of B sequences of L tokens from the fused q | k | v rows
+    (B*L, 3*H*dk): key j visible to query i iff j <= i and j < klen[b]; lse (B*H*L) the row log-sum-exp.  Rows at
+    or beyond klen[b] are written as zeros."""
+    _f32(qkv, ctx, lse)
+    D = H * dk
+    assert klen_i32.dtype == torch.int32 and klen_i32.is_cuda and klen_i32.numel() == B
+    assert qkv.is_contiguous() and ctx.is_contiguous() and lse.is_contiguous()
+    assert qkv.numel() == B * L * 3 * D and ctx.numel() == B * L * D and lse.numel() == B * H * L
+    _native.call("esp_causal_attn_fwd", _p(qkv), _p(klen_i32), _p(ctx), _p(lse), B, L, H, dk, _st())
+    return ctx
+
+
+def causal_attn_bwd(qkv, klen_i32, dctx, lse, dqkv, B, L, H, dk):
+    """dqkv (B*L, 3*H*dk) = dq | dk | dv of causal_attn_fwd for the output gradient dctx (probabilities recomputed
+    from qkv and lse); every element is written."""
+    _f32(qkv, dctx, lse, dqkv)
+    D = H * dk
+    assert klen_i32.dtype == torch.int32 and klen_i32.is_cuda and klen_i32.numel() == B
+    assert qkv.is_contiguous() and dctx.is_contiguous() and lse.is_contiguous() and dqkv.is_contiguous()
+    assert qkv.numel() == B * L * 3 * D and dctx.numel() == B * L * D and lse.numel() == B * H * L
+    assert dqkv.numel() == qkv.numel()
+    _native.call("esp_causal_attn_bwd", _p(qkv), _p(klen_i32), _p(dctx), _p(lse), _p(dqkv), B, L, H, dk, _st())
+    return dqkv
+
+
+def lm_front_fwd(x, gamma, beta, eps, y, mean, rstd, *, pe=None, xscale=1.0, L=1, p1=0.0, seed1=0, p2=0.0, seed2=0):
+    """y = drop2(relu(drop1(LN(x))) * xscale + pe[r % L]) (pe None: relu(drop1(LN(x)))): the LM input layer's
+    LayerNorm -> Dropout -> ReLU -> positional step in training form (esp_lm_front_fwd); mean / rstd (rows) saved
+    for the backward.  x, y (rows, D) contiguous."""
+    rows, D = x.shape
+    _f32(x, gamma, beta, y, mean, rstd, pe)
+    assert x.is_contiguous() and y.is_contiguous() and y.shape == x.shape
+    assert mean.numel() == rows and rstd.numel() == rows
+    if pe is not None:
+        assert pe.is_contiguous() and pe.shape[1] == D
+    _native.call("esp_lm_front_fwd", _p(x), _p(gamma), _p(beta), float(eps), float(xscale), _p(pe), int(L),
+                 pe.shape[0] if pe is not None else 0, float(p1), seed1, float(p2), seed2, _p(y), _p(mean), _p(rstd),
+                 rows, D, _st())
+    return y
+
+
+def lm_front_bwd(dy, x, gamma, beta, mean, rstd, dx, dgamma, dbeta, *, has_pe=False, xscale=1.0, p1=0.0, seed1=0,
+                 p2=0.0, seed2=0):
+    """The adjoint of lm_front_fwd: dx (overwritten) the gradient of the LayerNorm input, dgamma / dbeta
+    accumulated (+=) as layernorm_bwd does.  The masks are regenerated from the seeds, the ReLU decision from x and
+    the saved statistics."""
+    rows, D = x.shape
+    _f32(dy, x, gamma, beta, mean, rstd, dx, dgamma, dbeta)
+    assert dy.is_contiguous() and x.is_contiguous() and dx.is_contiguous() and dy.shape == x.shape == dx.shape
+    dz = torch.empty_like(dy)
+    n = _wsize("esp_layernorm_bwd", rows, D)
+    ws = _ws(WS, "esp_lm_front_bwd", n, x.device)
+    _native.call("esp_lm_front_bwd", _p(dy), _p(x), _p(gamma), _p(beta), _p(mean), _p(rstd), float(xscale),
+                 int(has_pe), float(p1), seed1, float(p2), seed2, _p(dz), _p(dx), _p(dgamma), _p(dbeta), rows, D,
+                 _p(ws), n, _st())
+    _guard_post("esp_lm_front_bwd", ws, n)
+    return dx
+
+
 # ----------------------------------------------------------------------------- contextual block Transformer
 # The block attention of the contextual block encoder on esp_block_attn_fwd / _bwd (one fused kernel each way, no
 # score tensor); False, or a shape outside the fused kernel's limits: MultiHeadedAttention's generic kernels with a

@@ -1,6 +1,6 @@
 """TransformerLM -- drop-in for espnet2/lm/transformer_lm.py:12-131 (over espnet1 transformer/encoder.py with
-input_layer="linear"), inference only: perplexity / validation loss (forward) and the shallow-fusion scorer
-(score / batch_score).
+input_layer="linear"): perplexity / validation loss (forward, inference only), the shallow-fusion scorer
+(score / batch_score) and the training step (run_forward / run_backward, driven by ESPnetLanguageModel).
 
 Embedding(V, embed_unit) -> Linear(embed_unit, att_unit) -> torch.nn.LayerNorm (eps 1e-5) -> ReLU -> positional step
 (identity for pos_enc None; x*sqrt(att_unit) + pe for "sinusoidal") -> `layer` pre-LN blocks [x += MHA(LN x) causal;
@@ -17,10 +17,21 @@ cache class and its two state forms: a DecoderCache whose rows are ys' rows, or 
 RowState / None).  With kernels.LM_STEP_FUSED and at most kernels.LM_STEP_MAX_ROWS rows a layer step is 5 launches
 on esp_step_linear (LN + qkv + cache write; masked attention; out-proj + residual; LN + w_1 + ReLU; w_2 + residual);
 otherwise the same step runs on the generic kernels (kernels.lm_step_linear: LayerNorm, linear_fwd, a cache write).
+
+Training (run_forward / run_backward, explicit like the encoders): embedding gather -> embed.0 -> the input layer's
+tail in training form (esp_lm_front_fwd: LayerNorm -> Dropout -> ReLU -> positional step) -> the layers -> after_norm
+-> decoder; every parameter gradient lands in flat.grad.  The layers' _attn_fwd / _attn_bwd are overridden here
+(_lm_attn_fwd / _lm_attn_bwd): their self-attention core runs on esp_causal_attn_fwd / _bwd (one launch each way, no
+score tensor) when kernels.LM_ATTN_FUSED and kernels.causal_attn_ok(L, d_k) hold, else on MultiHeadedAttention's
+generic kernels.  Dropout sites and rates are the
+reference's: the input layer's Dropout, each layer's two residual dropouts and the FFN's inner dropout at
+dropout_rate; PositionalEncoding's own dropout ("sinusoidal" only) at the espnet1 Encoder's default
+positional_dropout_rate 0.1, which the reference's TransformerLM does not override; no attention dropout (0.0).
 """
 from __future__ import annotations
 
 import math
+import types
 from typing import Any, Optional, Tuple
 
 import numpy as np
@@ -31,7 +42,7 @@ from .. import kernels as K
 from ..asr.decoder.transformer_decoder import DecoderCache, RowState, merge_row_states
 from ..asr.encoder.abs_encoder import pos_table
 from ..asr.encoder.transformer_encoder import TransformerEncoderLayer
-from ..blocks import LayerNorm, Linear, MultiHeadedAttention, PositionwiseFeedForward, Seeds, empty
+from ..blocks import Ctx, LayerNorm, Linear, MultiHeadedAttention, PositionwiseFeedForward, Seeds, empty, grad_buf
 from ..flat import FlatParams
 
 
@@ -46,6 +57,55 @@ def _ln(norm: LayerNorm):
     return norm.weight, norm.bias, norm.eps
 
 
+# espnet1 Encoder.__init__'s default, handed to pos_enc_class: the reference's TransformerLM passes dropout_rate only
+POSITIONAL_DROPOUT_RATE = 0.1
+
+
+def _lm_attn_fwd(self, h, resid, klen, B, T, seeds, training):
+    """TransformerEncoderLayer._attn_fwd of the LM's layers (bound to each layer by _Encoder): the self-attention
+    core (scores, mask, softmax, P.V) on the fused esp_causal_attn_fwd for the shapes it serves; the projections and
+    the residual dropout stay the GEMMs MultiHeadedAttention uses.  The dropout seeds are drawn as the generic path
+    draws them, so both paths see the same masks."""
+    sa = self.self_attn
+    H, dk = sa.h, sa.d_k
+    if not (K.LM_ATTN_FUSED and K.causal_attn_ok(T, dk)):
+        return TransformerEncoderLayer._attn_fwd(self, h, resid, klen, B, T, seeds, training)
+    D = H * dk
+    w, b = sa._w(("linear_q", "linear_k", "linear_v"))
+    qkv = empty(B * T, 3 * D, like=h)
+    K.linear_fwd(h, w, b, qkv)
+    ctx = empty(B * T, D, like=h)
+    lse = empty(B * H * T, like=h)
+    K.causal_attn_fwd(qkv, klen, ctx, lse, B, T, H, dk)
+    seeds.next()  # the generic path's attention-dropout seed (the LM's rate is 0.0)
+    out = empty(B * T, D, like=h)
+    pr = self.p if training else 0.0
+    so = seeds.next()
+    sa.linear_out.fwd(ctx, out, drop_p=pr, seed=so, R=resid, beta=1.0)
+    return out, Ctx(fused=True, xq=h, qkv=qkv, ctx=ctx, lse=lse, klen=klen, pr=pr, so=so, B=B, T=T)
+
+
+def _lm_attn_bwd(self, c, d):
+    """The adjoint of _lm_attn_fwd (the generic path's own when the forward took it)."""
+    if not c.get("fused"):
+        return TransformerEncoderLayer._attn_bwd(self, c, d)
+    sa = self.self_attn
+    H, dk = sa.h, sa.d_k
+    D = H * dk
+    dz = grad_buf(d)
+    K.scale_dropout(d, dz, drop_p=c.pr, seed=c.so)
+    dctx = sa.linear_out.bwd(dz, c.ctx)
+    dqkv = empty(c.B * c.T, 3 * D, like=d)
+    K.causal_attn_bwd(c.qkv, c.klen, dctx, c.lse, dqkv, c.B, c.T, H, dk)
+    names = ("linear_q", "linear_k", "linear_v")
+    w, _ = sa._w(names)
+    gw, gb = sa._w(names, grad=True)
+    K.linear_bwd_weight(dqkv, c.xq, gw, gb)
+    dx = empty(c.B * c.T, D, like=d)
+    K.linear_bwd_data(dqkv, w, dx)
+    return dx
+
+
 class _Encoder(nn.Module):
     """Parameter layout of the espnet1 Encoder with input_layer="linear" (embed.0 Linear, embed.1 torch LayerNorm;
     embed.2-4 -- Dropout, ReLU, the positional class -- hold no parameters)."""
@@ -58,6 +118,9 @@ class _Encoder(nn.Module):
                                     PositionwiseFeedForward(att_unit, unit, dropout_rate, K.ACT_RELU), dropout_rate,
                                     causal=True)
             for _ in range(layer)])
+        for l in self.encoders:  # the LM's attention core, local to the LM: the layer class stays the encoders' own
+            l._attn_fwd = types.MethodType(_lm_attn_fwd, l)
+            l._attn_bwd = types.MethodType(_lm_attn_bwd, l)
         self.after_norm = LayerNorm(att_unit)
 
 
@@ -72,6 +135,8 @@ class TransformerLM(AbsLM):
         self.encoder = _Encoder(embed_unit, att_unit, head, unit, layer, dropout_rate)
         self.decoder = Linear(att_unit, vocab_size)
         self.vocab_size, self.embed_unit, self.D, self.h = vocab_size, embed_unit, att_unit, head
+        self.dropout_rate = dropout_rate
+        self.positional_dropout_rate = POSITIONAL_DROPOUT_RATE  # PositionalEncoding's own dropout ("sinusoidal")
         self.flat: Optional[FlatParams] = None
         self._zero_pe = None
 
@@ -128,6 +193,47 @@ class TransformerLM(AbsLM):
             y, _ = self.encoder.after_norm.fwd(x)
             logits = self.decoder.fwd(y)
         return logits.view(B, L, -1), None
+
+    # ------------------------------------------------------------------ training step
+    def run_forward(self, tok: torch.Tensor, klen: torch.Tensor, B: int, L: int, seeds: Seeds, training: bool):
+        """tok (B*L,) int64 and klen (B,) int32 on the device -> (logits (B*L, V), saved).  Device work only: no
+        host synchronisation, no host copy (a captured graph replays it).  Rows at or beyond klen[b] are padding:
+        no key reads them and the caller's loss gradient is zero there."""
+        dev = self._ready()
+        emb = self.encoder.embed
+        e = self._gather(tok)
+        lin = emb[0].fwd(e)
+        p1 = self.dropout_rate if training else 0.0
+        p2 = self.positional_dropout_rate if training else 0.0
+        s1, s2 = seeds.next(), seeds.next()
+        pe = self._pe(L, dev)
+        x, mean, rstd = torch.empty_like(lin), empty(B * L, like=lin), empty(B * L, like=lin)
+        K.lm_front_fwd(lin, emb[1].weight, emb[1].bias, emb[1].eps, x, mean, rstd, pe=pe, xscale=math.sqrt(self.D),
+                       L=L, p1=p1, seed1=s1, p2=p2, seed2=s2)
+        ctxs = []
+        for layer in self.encoder.encoders:
+            x, c = layer.fwd(x, klen, B, L, seeds, training)
+            ctxs.append(c)
+        y, c_an = self.encoder.after_norm.fwd(x)
+        logits = self.decoder.fwd(y)
+        return logits, Ctx(tok=tok, e=e, lin=lin, mean=mean, rstd=rstd, p1=p1, p2=p2, s1=s1, s2=s2,
+                           has_pe=pe is not None, layers=ctxs, an=c_an, y=y)
+
+    def run_backward(self, saved: Ctx, dlogits: torch.Tensor) -> None:
+        """The adjoint of run_forward for dlogits (B*L, V): every parameter gradient is accumulated into
+        flat.grad."""
+        enc = self.encoder
+        dy = self.decoder.bwd(dlogits, saved.y)
+        d = enc.after_norm.bwd_new(saved.an, dy)
+        for layer, c in zip(reversed(enc.encoders), reversed(saved.layers)):
+            d = layer.bwd(c, d)
+        ln = enc.embed[1]
+        dlin = torch.empty_like(d)
+        K.lm_front_bwd(d, saved.lin, ln.weight, ln.bias, saved.mean, saved.rstd, dlin, ln.weight.grad, ln.bias.grad,
+                       has_pe=saved.has_pe, xscale=math.sqrt(self.D), p1=saved.p1, seed1=saved.s1, p2=saved.p2,
+                       seed2=saved.s2)
+        de = enc.embed[0].bwd(dlin, saved.e)
+        K.embed_bwd(saved.tok, de, self.embed.weight.grad, 1.0, 0.0, 0)
 
     # ------------------------------------------------------------------ one-step scorer
     def _eval_only(self, what: str):

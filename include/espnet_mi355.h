@@ -653,6 +653,39 @@ int esp_maskctc_init(const float* lp, int T, int V, int blank, long long mask_to
                      float* flp, long long* y_in, float* tok_logp, float* tok_prob, int* counts, void* stream);
 int esp_maskctc_fill(const float* logits, int L, int V1, long long* y_in, long long mask_token, int k, void* stream);
 
+/* ---- ABI 42: Transformer LM training (espnet2/lm/transformer_lm.py forward, espnet2/lm/espnet_model.py).
+ *
+ * esp_causal_attn_fwd / _bwd (csrc/causal_attn.hip): causal self-attention of B sequences of L tokens, one workgroup
+ * per (sequence, head), exact fp32 FMA, no dropout.  qkv: (B*L, 3*H*dk) rows q | k | v (the fused projection's
+ * output); ctx / dctx: (B*L, H*dk); lse: B*H*L floats, row (b*H + h)*L + i; klen: B device int32 (clamped to [0, L]).
+ * Key j is visible to query i iff j <= i and j < klen[b]; scale 1 / sqrt(dk).  The forward writes ctx and the row
+ * log-sum-exp only; the backward recomputes the probabilities from qkv and lse and writes every element of dqkv
+ * (dq | dk | dv; no pre-zeroing, no atomics, bit-reproducible).  Query rows i >= klen[b]: ctx = 0, lse = 0, dq = 0;
+ * key rows j >= klen[b]: dk = dv = 0.  Served: dk in {16, 32, 64, 128}, 1 <= L <= 64 for every dk (dk = 128, L = 64:
+ * 132 KiB of LDS in the backward); anything else: status -1, nothing launched.  qkv / ctx / dctx / dqkv 16-byte
+ * aligned.
+ *
+ * esp_lm_front_fwd / _bwd (csrc/lm_step.hip): the LM input layer's tail in training form (espnet1 encoder.py
+ * input_layer "linear": LayerNorm -> Dropout(p1) -> ReLU -> positional step), rows of D floats, row r at position
+ * r % L:  y = drop2(relu(drop1(LN(x))) * xscale + pe[r % L]);  pe NULL (the empty positional step): y =
+ * relu(drop1(LN(x))), no scale, no second dropout.  Dropout masks by element index r*D + c under seed1 / seed2.
+ * The forward saves mean / rstd (rows floats each); at p1 = 0 its values equal esp_step_ln_act's bit for bit.
+ * The backward takes dy, regenerates both masks, recomputes the ReLU decision from x and the saved statistics,
+ * writes the gradient of LN(x) to dz (rows*D floats of scratch, distinct from dy and dx) and runs esp_layernorm_bwd
+ * on it: dx (overwritten) the gradient of x, dgamma / dbeta accumulated (+=).  D % 4 == 0; work:
+ * esp_layernorm_bwd_workspace_bytes(rows, D). */
+int esp_causal_attn_fwd(const float* qkv, const int* klen, float* ctx, float* lse, int B, int L, int H, int dk,
+                        void* stream);
+int esp_causal_attn_bwd(const float* qkv, const int* klen, const float* dctx, const float* lse, float* dqkv, int B,
+                        int L, int H, int dk, void* stream);
+int esp_lm_front_fwd(const float* x, const float* gamma, const float* beta, float eps, float xscale, const float* pe,
+                     int L, int pe_rows, float p1, unsigned long long seed1, float p2, unsigned long long seed2,
+                     float* y, float* mean, float* rstd, int rows, int D, void* stream);
+int esp_lm_front_bwd(const float* dy, const float* x, const float* gamma, const float* beta, const float* mean,
+                     const float* rstd, float xscale, int has_pe, float p1, unsigned long long seed1, float p2,
+                     unsigned long long seed2, float* dz, float* dx, float* dgamma, float* dbeta, int rows, int D,
+                     float* work, long work_bytes, void* stream);
+
 /* esp_conv1_dgrad (csrc/conv.hip): the feature gradient of the subsampling's first convolution (3 x 3, stride 2),
  * dx (B, T, F) = the adjoint of conv1 applied to dz1 (B, T1, F1, D) (ReLU mask already applied), W (D, 9).  Training
  * does not call it (the features are data); an encoder's run_backward forms it on request. */
