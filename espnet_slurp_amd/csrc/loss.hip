@@ -3,7 +3,8 @@
 //   * CTC alpha/beta (one block per utterance and direction, the two recursions run
 //     concurrently) and the per-frame gradient w.r.t. the logits, following PyTorch's
 //     CPU ctc_loss (max-shifted 3-way log-sum-exp, zero_infinity, grad
-//     exp(lp) - exp(lcab + nll - lp), then log_softmax's adjoint)   [ctc.py:39-60]
+//     exp(lp) - sum over the class's states of exp(alpha + beta + nll - lp), summed in a fixed
+//     order without atomics, then log_softmax's adjoint)   [ctc.py:39-60]
 //   * label-smoothed KL (t*log t included) + gradient + th_accuracy counts
 //     [label_smoothing_loss.py:41-63, nets_utils.py:299-320]
 //   * deterministic final reduction to the reported scalars
@@ -114,8 +115,14 @@ __global__ __launch_bounds__(CTC_NT) void ctc_alpha_beta_kernel(const float* __r
   }
 }
 
-// grid (T, B): gradient of gscale * nll_b w.r.t. the logits for frame t of utterance b
+// grid (T, B): gradient of gscale * nll_b w.r.t. the logits for frame t of utterance b.
+// Each state's share of the posterior is formed directly, p_s = exp(alpha_s + beta_s + nll - lp[lab_s]): its
+// log is at most 0, so nothing is shifted and nothing can overflow (alpha + beta holds lp twice and spans a far
+// wider range than the posterior does).  The per-class sums run in a fixed order without atomics: the blank
+// (every even state) by a strided partial sum per thread and the block reduction; a label by the thread of its
+// first occurrence in the target, which adds the p of every occurrence in target order.
 constexpr int MAXV_LDS = 8192;
+struct alignas(8) CtcPL { float p; int l; };
 __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__ lp, const int64_t* __restrict__ labels,
                                                        int Umax, const int* __restrict__ ilen,
                                                        const int* __restrict__ tlen, int T, int V, int Smax, int blank,
@@ -123,8 +130,8 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
                                                        const double* __restrict__ nll, float gscale, int zero_infinity,
                                                        float* __restrict__ grad) {
   __shared__ float occ[MAXV_LDS];
+  __shared__ CtcPL pl[CTC_NT * CTC_SPT / 2];  // per target position u: p of state 2u + 1 and its label
   __shared__ float sh[16];
-  __shared__ double shd[16];
   const int t = blockIdx.x, b = blockIdx.y;
   const int Tb = ilen[b], U = tlen[b], S = 2 * U + 1;
   float* gr = grad + ((long)b * T + t) * V;
@@ -136,33 +143,38 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
   for (int c = threadIdx.x; c < V; c += blockDim.x) occ[c] = 0.f;
   const double* lat = la + ((long)b * T + t) * Smax;
   const double* lbt = lb + ((long)b * T + t) * Smax;
-  double m = -INFINITY;
-  for (int s = threadIdx.x; s < S; s += blockDim.x) m = fmax(m, lat[s] + lbt[s]);
-  m = esp::block_max<double>(m, shd);  // includes a barrier: occ is zeroed before the adds below
-  if (m != -INFINITY) {
-    for (int s = threadIdx.x; s < S; s += blockDim.x) {
-      const int l = (s & 1) ? (int)labels[(long)b * Umax + (s >> 1)] : blank;
-      const double v = lat[s] + lbt[s];
-      if (v != -INFINITY) atomicAdd(&occ[l], expf((float)(v - m)));
+  const float* lpt = lp + ((long)b * T + t) * V;
+  float pb = 0.f;  // this thread's states of the blank class, ascending
+  for (int s = threadIdx.x; s < S; s += blockDim.x) {
+    const int l = (s & 1) ? (int)labels[(long)b * Umax + (s >> 1)] : blank;
+    const double v = lat[s] + lbt[s];
+    const float p = v != -INFINITY ? expf((float)(v + nl - (double)lpt[l])) : 0.f;
+    if (s & 1) pl[s >> 1] = CtcPL{p, l};
+    if (l == blank) pb += p;
+  }
+  pb = esp::block_sum<float>(pb, sh);  // its barriers also publish occ = 0 and pl
+  if (threadIdx.x == 0) occ[blank] = pb;
+  for (int u = threadIdx.x; u < U; u += blockDim.x) {
+    const int l = pl[u].l;
+    bool first = l != blank;  // a blank inside the target is in pb already
+    float a = 0.f;
+    // no early exit: without a data-dependent branch the LDS reads of several steps are in flight together
+#pragma unroll 8
+    for (int w = 0; w < U; ++w) {
+      const CtcPL e = pl[w];
+      const bool same = e.l == l;
+      first = first && !(same && w < u);
+      a += same ? e.p : 0.f;
     }
+    if (first) occ[l] = a;
   }
   __syncthreads();
-  const float* lpt = lp + ((long)b * T + t) * V;
-  const double mn = m + nl;  // log occupancy offset: exp(lcab + nll - lp) = occ * exp(m + nll - lp)
   float gs = 0.f;
-  for (int c = threadIdx.x; c < V; c += blockDim.x) {
-    const float l = lpt[c];
-    const float o = occ[c];
-    const float q = o > 0.f ? o * expf((float)(mn - (double)l)) : 0.f;
-    gs += expf(l) - q;
-  }
+  for (int c = threadIdx.x; c < V; c += blockDim.x) gs += expf(lpt[c]) - occ[c];
   gs = esp::block_sum<float>(gs, sh);
   for (int c = threadIdx.x; c < V; c += blockDim.x) {
-    const float l = lpt[c];
-    const float o = occ[c];
-    const float q = o > 0.f ? o * expf((float)(mn - (double)l)) : 0.f;
-    const float e = expf(l);
-    gr[c] = (e - q) * gscale - e * (gs * gscale);
+    const float e = expf(lpt[c]);
+    gr[c] = (e - occ[c]) * gscale - e * (gs * gscale);
   }
 }
 

@@ -57,7 +57,7 @@ def ctc_loss_np(logits, ilens, targets, tlens, blank=0, zero_infinity=True):
                     v = la[t - 1, s]
                     if s >= 1:
                         v = _lse(v, la[t - 1, s - 1])
-                    if s >= 2 and lab[s] != blank and lab[s] != lab[s - 2]:
+                    if s >= 2 and lab[s] != lab[s - 2]:  # as ATen and the kernel: no separate blank test
                         v = _lse(v, la[t - 1, s - 2])
                     la[t, s] = v + lp[t, b, lab[s]]
             lb[Tb - 1, S - 1] = lp[Tb - 1, b, blank]
@@ -68,7 +68,7 @@ def ctc_loss_np(logits, ilens, targets, tlens, blank=0, zero_infinity=True):
                     v = lb[t + 1, s]
                     if s + 1 < S:
                         v = _lse(v, lb[t + 1, s + 1])
-                    if s + 2 < S and lab[s] != blank and lab[s] != lab[s + 2]:
+                    if s + 2 < S and lab[s] != lab[s + 2]:
                         v = _lse(v, lb[t + 1, s + 2])
                     lb[t, s] = v + lp[t, b, lab[s]]
             ll = la[Tb - 1, S - 1] if S == 1 else _lse(la[Tb - 1, S - 1], la[Tb - 1, S - 2])
