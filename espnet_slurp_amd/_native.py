@@ -76,6 +76,8 @@ SIGNATURES = {
     "esp_csgu_fwd": [P, P, P, P, P, P, P, P, I, I, I, I, F, U64, P, P],
     "esp_csgu_bwd_gate": [P, P, P, P, P, P, P, P, P, L, I, P, P, I, I, I, I, F, U64, P, P],
     "esp_csgu_bwd_norm": [P, P, P, P, P, P, L, I, P, I, I, I, P, P],
+    "esp_ebf_merge_fwd": [P, P, P, P, L, I, I, I, I, I, P, P],
+    "esp_ebf_merge_bwd": [P, P, P, P, P, P, P, I, I, I, I, P, L, P, P],
     "esp_bn_swish_fwd": [P, P, P, P, P, P, P, P, F, F, I, I, P, L, I, P, P],
     "esp_bn_swish_eval": [P, P, P, P, P, P, F, I, I, P, P, P],
     "esp_bn_swish_fwd_planes": [P, P, P, P, L, L, I, P, P, P, P, F, F, I, I, P, L, I, P, P],
@@ -148,6 +150,7 @@ SIGNATURES = {
     "esp_layernorm_bwd_workspace_bytes": [I, I],
     "esp_colsum_workspace_bytes": [I, I],
     "esp_dwconv1d_wgrad_workspace_bytes": [I, I, I, I],
+    "esp_ebf_merge_bwd_workspace_bytes": [I, I, I, I],
     "esp_bn_swish_fwd_workspace_bytes": [I, I],
     "esp_bn_swish_bwd_workspace_bytes": [I, I],
     "esp_conv1_wgrad_workspace_bytes": [I, I, I, I],

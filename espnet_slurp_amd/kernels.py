@@ -998,6 +998,77 @@ def csgu_bwd(v, mean, rstd, gamma, beta, W, bias, dout, dv, dgamma, dbeta, dW, d
     return dv
 
 
+# ---- the E-Branchformer's enhanced merge (ebf_merge.hip): xc (B*T, 2D) holds the two branch outputs side by side
+# True: esp_ebf_merge_fwd / _bwd, one pass each.  False: the same mathematics composed from esp_dwconv1d (+ an
+# add), esp_dwconv1d(flip), esp_dwconv1d_wgrad and esp_colsum -- the on-device yardstick of the tests and of
+# tools/bench_ebranchformer.py, which measured the default
+EBF_MERGE_FUSED = True
+EBF_MERGE_KMAX = 31  # esp_ebf_merge_*: taps
+_ONES = {}
+
+
+def _masked_rows(x, Bn, T, C, tvalid):
+    """x with the rows at or after *tvalid zeroed (a one-tap depthwise pass with unit weights), x itself
+    without tvalid (the composed merge only)."""
+    if tvalid is None:
+        return x
+    key = (C, str(x.device))
+    if key not in _ONES:
+        _ONES[key] = torch.ones(C, 1, dtype=torch.float32, device=x.device)
+    y = torch.empty_like(x)
+    dwconv1d(x, _ONES[key], None, y, Bn, T, C, 1, tvalid=tvalid)
+    return y
+
+
+def ebf_merge_fwd(xc, W, bias, Bn, T, k, tvalid=None, planes=None):
+    """u = xc + dwconv_k(xc) + bias (B*T, C): Planes in the current compute mode (planes_mode: only merge_proj's
+    GEMMs read it), else fp32.  planes: 0 / 1 / 3 instead of the mode's choice (tests)."""
+    M, C = xc.shape
+    _f32(xc, W, bias)
+    assert M == Bn * T and xc.is_contiguous() and W.is_contiguous() and W.numel() == C * k
+    npl = planes_mode() if planes is None else planes
+    u = Planes(M, C, xc.device, npl) if npl else torch.empty_like(xc)
+    if EBF_MERGE_FUSED:
+        _native.call("esp_ebf_merge_fwd", _p(xc), _p(W), _p(bias), _p(u.buf) if npl else _p(u), u.ps if npl else 0, npl,
+                     Bn, T, C, k, _p(tvalid), _st())
+        return u
+    y = torch.empty_like(xc)
+    dwconv1d(xc, W, bias, y, Bn, T, C, k, tvalid=tvalid)
+    if npl:
+        scale_dropout(_masked_rows(xc, Bn, T, C, tvalid), y, r=y, beta=1.0)
+        return scale_dropout(y, u)
+    return scale_dropout(_masked_rows(xc, Bn, T, C, tvalid), u, r=y, beta=1.0)
+
+
+def ebf_merge_bwd(du, xc, W, dW, dbias, Bn, T, k, tvalid=None):
+    """From du = dL/du (B*T, C) fp32: (d1, d2), the contiguous (B*T, C/2) halves of du + conv^T(du); dW and dbias
+    are accumulated (+=)."""
+    M, C = xc.shape
+    D = C // 2
+    _f32(du, xc, W, dW, dbias)
+    assert M == Bn * T and du.shape == (M, C) and du.is_contiguous() and xc.is_contiguous() and W.is_contiguous()
+    d1 = torch.empty(M, D, dtype=torch.float32, device=du.device)
+    d2 = torch.empty(M, D, dtype=torch.float32, device=du.device)
+    if EBF_MERGE_FUSED:
+        n = _wsize("esp_ebf_merge_bwd", Bn, T, C, k)
+        ws = _ws(WS, "esp_ebf_merge_bwd", n, du.device)
+        _native.call("esp_ebf_merge_bwd", _p(du), _p(xc), _p(W), _p(d1), _p(d2), _p(dW), _p(dbias), Bn, T, C, k, _p(ws),
+                     n, _p(tvalid), _st())
+        _guard_post("esp_ebf_merge_bwd", ws, n)
+        return d1, d2
+    du = _masked_rows(du, Bn, T, C, tvalid)
+    colsum(du, dbias, accumulate=True)
+    dwconv1d_wgrad(du, xc, dW, Bn, T, C, k, tvalid=tvalid)
+    dx = torch.empty_like(du)
+    dwconv1d(du, W, None, dx, Bn, T, C, k, flip=True, tvalid=tvalid)
+    scale_dropout(du, dx, r=dx, beta=1.0)
+    d1.zero_()
+    d2.zero_()
+    add2d(dx, C, d1, D, M, D)
+    add2d(dx, C, d2, D, M, D, x_off=D)
+    return d1, d2
+
+
 def bn_swish_fwd(y, gamma, beta, s, mean, rstd, run_mean, run_var, momentum=0.1, eps=1e-5, T=0, tvalid=None):
     """s: fp32 [M, D] or Planes (esp_bn_swish_fwd_planes)."""
     M, D = y.shape

@@ -259,6 +259,24 @@ int esp_dwconv1d_wgrad(const float* dy, const float* x, float* dW, int Bn, int T
  *   esp_csgu_bwd_norm: from dn = dL/dn: dv[:, C:] = LN'(dn) GELU'(v_g) and pxh = dn * xhat (B*T, C), whose column
  *     sum is the LayerNorm weight gradient (dn's is the bias gradient).
  * Between the two backward calls: dn = esp_dwconv1d(dg, flip), esp_dwconv1d_wgrad(dg, n), esp_colsum(dg). */
+/* The E-Branchformer's enhanced merge around merge_proj (csrc/ebf_merge.hip; e_branchformer_encoder.py:158-163; a
+ * pure addition to the ABI above).  xc (B*T, C) is the concatenation [x1, x2] of the two branch outputs (C = 2D), W (C, k)
+ * and bias (C) are depthwise_conv_fusion's:
+ *   u[b,t,c] = xc[b,t,c] + bias[c] + sum_j W[c,j] xc[b, t + j - (k-1)/2, c]
+ * over each utterance's own T rows (zero outside [0, T) and at or after *tvalid; no length mask: padded frames of a
+ * short utterance are read like any other).  Rows at or after *tvalid are written as 0.  C % 8 == 0, k odd and
+ * <= 31, any T >= 1, 16-B aligned tensors; other arguments fail with status -1.
+ *   esp_ebf_merge_fwd: u (B*T, C), fp32 (nplanes 0) or bf16 planes (nplanes 1 / 3, plane p at u + p * pstride bf16
+ *     elements, row pitch C): merge_proj's operand format.
+ *   esp_ebf_merge_bwd: from du = dL/du (B*T, C; rows at or after *tvalid are not read): the input gradient
+ *     du + conv^T(du) as its two contiguous (B*T, C/2) halves d1 | d2, and dW (C, k) += sum du[b,t,c] xc[b,t+j-pad,c],
+ *     dbias (C) += sum du[b,t,c].  The sums are formed per block in the workspace
+ *     (esp_ebf_merge_bwd_workspace_bytes) and added in a fixed order by a second kernel (no atomics: repeated
+ *     launches give the same bits). */
+int esp_ebf_merge_fwd(const float* xc, const float* W, const float* bias, void* u, long pstride, int nplanes, int B,
+                      int T, int C, int k, const int* tvalid, void* stream);
+int esp_ebf_merge_bwd(const float* du, const float* xc, const float* W, float* d1, float* d2, float* dW, float* dbias,
+                      int B, int T, int C, int k, float* work, long work_bytes, const int* tvalid, void* stream);
 int esp_csgu_stats(const float* v, long M, int C, float eps, float* mean, float* rstd, void* stream);
 int esp_csgu_fwd(const float* v, const float* mean, const float* rstd, const float* gamma, const float* beta,
                  const float* W, const float* bias, float* o, int B, int T, int C, int k, float drop_p,
@@ -699,6 +717,7 @@ long esp_grad_norm_workspace_bytes(long n);
 long esp_layernorm_bwd_workspace_bytes(int M, int D);
 long esp_colsum_workspace_bytes(int M, int N);
 long esp_dwconv1d_wgrad_workspace_bytes(int Bn, int T, int D, int K);
+long esp_ebf_merge_bwd_workspace_bytes(int B, int T, int C, int k);
 long esp_bn_swish_fwd_workspace_bytes(int M, int D);
 long esp_bn_swish_bwd_workspace_bytes(int M, int D);
 long esp_conv1_wgrad_workspace_bytes(int B, int T, int F, int D);
