@@ -145,6 +145,13 @@ SIGNATURES = {
     "esp_lm_front_bwd": [P, P, P, P, P, P, F, I, F, U64, F, U64, P, P, P, P, I, I, P, L, P],
     "esp_maskctc_init": [P, I, I, I, ctypes.c_longlong, ctypes.c_double, P, P, P, P, P, P, P],
     "esp_maskctc_fill": [P, I, I, P, ctypes.c_longlong, I, P],
+    "esp_rnnt_joint_fwd": [P, P, P, I, I, I, I, I, P],
+    "esp_rnnt_joint_bwd": [P, P, P, P, P, P, I, I, I, I, I, P, L, P],
+    "esp_rnnt_logprobs": [P, P, P, P, I, I, I, I, P, L, P],
+    "esp_rnnt_alpha_beta": [P, P, I, I, I, P, L, P, P],
+    "esp_rnnt_grad": [P, P, P, P, I, I, I, I, F, P, P, P, L, P],
+    "esp_lstm_cell_fwd": [P, L, P, L, P, L, P, P, L, P, L, P, L, P, L, I, I, P],
+    "esp_lstm_cell_bwd": [P, L, P, L, P, P, L, P, L, P, L, P, P, P, L, I, I, P],
     # workspace-size queries (host arithmetic; return bytes)
     "esp_grad_norm_workspace_bytes": [L],
     "esp_layernorm_bwd_workspace_bytes": [I, I],
@@ -156,6 +163,8 @@ SIGNATURES = {
     "esp_conv1_wgrad_workspace_bytes": [I, I, I, I],
     "esp_conv2_dgrad_workspace_bytes": [I],
     "esp_ctc_loss_workspace_bytes": [I, I, I],
+    "esp_rnnt_joint_bwd_workspace_bytes": [I, I, I, I],
+    "esp_rnnt_loss_workspace_bytes": [I, I, I],
     "esp_relpos_dp_workspace_bytes": [I, I, I],
 }
 _RESTYPES = {"esp_last_error": ctypes.c_char_p, "esp_abi_version": I, "esp_attn_slot_check_errors": I, "esp_set_gemm_compute": I,

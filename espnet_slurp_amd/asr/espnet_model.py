@@ -100,8 +100,8 @@ class ESPnetASRModel(AbsESPnetModel):
                  lang_token_id: int = -1):
         assert 0.0 <= ctc_weight <= 1.0, ctc_weight
         super().__init__()
-        if preencoder is not None or postencoder is not None or joint_network is not None:
-            raise NotImplementedError("pre-/post-encoder/transducer are not on the hot path")
+        if preencoder is not None or postencoder is not None:
+            raise NotImplementedError("pre-/post-encoder are not on the hot path")
         if frontend is not None and not hasattr(frontend, "apply_prepared"):
             raise NotImplementedError("frontend: only the native DefaultFrontend (frontend: default)")
         if lang_token_id != -1:
@@ -123,13 +123,35 @@ class ESPnetASRModel(AbsESPnetModel):
         self.encoder = encoder
         if getattr(encoder, "interctc_use_conditioning", False):  # espnet_model.py:96-101
             encoder.conditioning_layer = Linear(vocab_size, encoder.output_size())
-        self.decoder = None if ctc_weight == 1.0 else decoder
-        self.ctc = None if ctc_weight == 0.0 else ctc
+        # the (RNN-)Transducer branch of the reference's model class (espnet_model.py:103-134)
+        self.use_transducer_decoder = joint_network is not None
         self.lsm_weight = lsm_weight
         self.length_normalized_loss = length_normalized_loss
-        # eval-mode cer_ctc / cer / wer (espnet_model.py:152-154, 515-540)
-        self.error_calculator = (ErrorCalculator(token_list, sym_space, sym_blank, report_cer, report_wer)
-                                 if report_cer or report_wer else None)
+        if self.use_transducer_decoder:
+            if interctc_weight != 0.0:
+                raise NotImplementedError("interctc_weight != 0 with a transducer (joint_network): intermediate CTC "
+                                          "is served on the CTC/attention model only")
+            if getattr(encoder, "interctc_use_conditioning", False):
+                raise NotImplementedError("interctc_use_conditioning with a transducer (joint_network): "
+                                          "self-conditioned CTC is served on the CTC/attention model only")
+            from .transducer.error_calculator import ErrorCalculatorTransducer
+            self.decoder = decoder
+            self.joint_network = joint_network
+            # the reference's quirk: the CTC error calculator exists only when both report flags are off
+            self.error_calculator = None
+            self.error_calculator_trans = None
+            if report_cer or report_wer:
+                self.error_calculator_trans = ErrorCalculatorTransducer(
+                    decoder, joint_network, token_list, sym_space, sym_blank, report_cer=report_cer,
+                    report_wer=report_wer)
+            elif ctc_weight != 0:
+                self.error_calculator = ErrorCalculator(token_list, sym_space, sym_blank, report_cer, report_wer)
+        else:
+            self.decoder = None if ctc_weight == 1.0 else decoder
+            # eval-mode cer_ctc / cer / wer (espnet_model.py:152-154, 515-540)
+            self.error_calculator = (ErrorCalculator(token_list, sym_space, sym_blank, report_cer, report_wer)
+                                     if report_cer or report_wer else None)
+        self.ctc = None if ctc_weight == 0.0 else ctc  # (registered after the decoder, as the reference's is)
         self.extract_feats_in_collect_stats = extract_feats_in_collect_stats
         self.flat: Optional[FlatParams] = None
         if self.blank_id != 0:
@@ -140,7 +162,7 @@ class ESPnetASRModel(AbsESPnetModel):
         """Move parameters into one flat HBM buffer (+ flat grads).  Call once, after .to(device)."""
         device = device or next(self.parameters()).device
         self.flat = FlatParams(self, device)
-        for m in (self.encoder, self.decoder):
+        for m in (self.encoder, self.decoder, getattr(self, "joint_network", None)):
             if m is not None and hasattr(m, "attach_flat"):
                 m.attach_flat(self.flat)
         return self.flat
@@ -169,7 +191,7 @@ class ESPnetASRModel(AbsESPnetModel):
         hs2d = hs.reshape(B * T, D)
         d = prep.dev
         hlens_i32 = d["hlens"]
-        state = {"hs2d": hs2d, "B": B, "T": T}
+        state = {"hs2d": hs2d, "B": B, "T": T, "prep_dev": d}
         nll = grad_ctc = None
         inter = prep.get("inter")
         # (the encoder's intermediate branches also add ctc_lo gradient in its backward: the ctc module-done
@@ -182,6 +204,8 @@ class ESPnetASRModel(AbsESPnetModel):
             nll, grad_ctc, _ = self.ctc.loss_and_grad(hs2d, B, T, hlens_i32, d["ys"], d["tlens"], prep.Umax,
                                                       self.ctc_weight * (1.0 - w_ic) / B, want_grad=want_grad)
             state["grad_ctc"] = grad_ctc
+        if self.use_transducer_decoder:
+            return self._transducer_forward(hs2d, prep, seeds, want_grad, nll, state)
         nll_main = nll
         if inter:
             # loss_ctc of the loss = (1 - w) loss_ctc + w mean_l loss_interctc_l, each utterance's inf zeroed in
@@ -223,6 +247,49 @@ class ESPnetASRModel(AbsESPnetModel):
             out4[0:1].copy_(state["loss_ctc_main"])
         return out4, state
 
+    def _transducer_forward(self, hs2d, prep: "Prepared", seeds: Seeds, want_grad: bool, nll_ctc, state):
+        """The transducer branch of _heads_forward (espnet_model.py:247-269, 542-588): predictor, joint network,
+        lattice loss.  loss = loss_transducer + ctc_weight * loss_ctc with loss_transducer the batch mean of nll_b.
+        The gradient w.r.t. the logits is formed in the backward, in place over the saved logits."""
+        d = prep.dev
+        B, T, U1, V = state["B"], state["T"], prep.U1, self.vocab_size
+        dec2d, dsaved = self.decoder.run_forward(d["dec_in"], d["dec_in_grad"], seeds, self.training, keep=want_grad)
+        logits, jsaved = self.joint_network.run_forward(hs2d, dec2d, B, T, U1)
+        work = K.rnnt_workspace(B, T, U1, hs2d.device)
+        nll = torch.empty(B, dtype=torch.float64, device=hs2d.device)
+        K.rnnt_logprobs(logits, d["rnnt_target"], d["hlens"], d["rnnt_ulens"], B, T, U1, V, work)
+        K.rnnt_alpha_beta(d["hlens"], d["rnnt_ulens"], B, T, U1, work, nll)
+        # out: loss_ctc | loss_transducer | 0 | loss -- the heads' (others[0:3], loss) layout that HeadsFn and
+        # forward_prepared slice; slot 2 (the attention branch's accuracy) has no transducer counterpart
+        out = torch.zeros(4, dtype=torch.float32, device=hs2d.device)
+        self._batch_mean(nll, B, False, prep.denom, out[1:2])
+        if nll_ctc is not None:
+            self._batch_mean(nll_ctc, B, self.ctc.zero_infinity, prep.denom, out[0:1])
+            K.scale_dropout(out[0:1], out[3:4], alpha=self.ctc_weight, r=out[1:2], beta=1.0)
+        else:
+            out[3:4].copy_(out[1:2])
+        if want_grad:
+            state.update(rnnt=dict(logits=logits, work=work, nll=nll, joint=jsaved, dec=dsaved, U1=U1))
+        return out, state
+
+    @staticmethod
+    def _batch_mean(nll, B, zero_inf, denom, dst):
+        """dst[0] <- sum_b nll_b / B (fp64 per-utterance values, esp_reduce_losses' fixed-order sum)."""
+        red = torch.empty(5, dtype=torch.float32, device=nll.device)
+        K.reduce_losses(nll, B, zero_inf, None, None, 0, denom, 1.0, red)
+        dst.copy_(red[0:1])
+
+    def _transducer_backward(self, state, g_loss, dhs, hook):
+        r = state.pop("rnnt")
+        d = state["prep_dev"]
+        B, T, U1, V = state["B"], state["T"], r["U1"], self.vocab_size
+        g = K.rnnt_grad(r["logits"], d["rnnt_target"], d["hlens"], d["rnnt_ulens"], B, T, U1, V, 1.0 / B, r["nll"],
+                        r["work"], gdev=g_loss)
+        ddec = self.joint_network.run_backward(r["joint"], g, d["hlens"], d["rnnt_ulens"], dhs)
+        if hook is not None:
+            hook(self.joint_network)
+        self.decoder.run_backward(r["dec"], ddec, hook)
+
     def _heads_backward(self, state, g_loss, hook=None):
         hs2d = state["hs2d"]
         dhs = torch.zeros_like(hs2d) if self.ctc is None else torch.empty_like(hs2d)
@@ -237,7 +304,9 @@ class ESPnetASRModel(AbsESPnetModel):
                     K.scale_by_dev(gi, g_loss)
             if hook is not None and not state.get("inter_any"):
                 hook(self.ctc)
-        if self.decoder is not None:
+        if self.use_transducer_decoder:
+            self._transducer_backward(state, g_loss, dhs, hook)
+        elif self.decoder is not None:
             g = state["grad_att"]
             if state.get("inv_denom") is not None:
                 K.scale_by_dev(g, state["inv_denom"])
@@ -305,12 +374,35 @@ class ESPnetASRModel(AbsESPnetModel):
         if self.ctc is not None:
             host["ys"] = text_cpu
             host["tlens"] = tl_cpu.to(torch.int32)
-        if self.decoder is not None:
+        if self.use_transducer_decoder:
+            host.update(self._transducer_io(text_cpu))
+            prep["U1"] = int(text_cpu.shape[1]) + 1
+        elif self.decoder is not None:
             ys_in, ys_out, ys_in_lens = self._decoder_targets(text_cpu, tl_cpu, u_bucket, **target_draws)
             prep["L"] = int(ys_in.shape[1])
             host["ys_in"], host["ys_out"] = ys_in, ys_out
             host["ys_in_lens"] = ys_in_lens.to(torch.int32)
         return prep
+
+    def _transducer_io(self, text_cpu: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """get_transducer_task_io (espnet2/asr_transducer/utils.py:127-190) on the host, at the padded width of
+        text_cpu (B, Umax): dec_in = [blank] + y padded with blank (B, Umax + 1), rnnt_target = y padded with blank
+        (B, Umax), rnnt_ulens = the label counts; t_len is the encoder's hlens.  dec_in_grad is dec_in with the
+        embedding's padding index replaced by -1: the rows of the embedding that get a gradient."""
+        B, Umax = text_cpu.shape
+        blank = self.blank_id
+        dec_in = torch.full((B, Umax + 1), blank, dtype=torch.long)
+        target = torch.full((B, Umax), blank, dtype=torch.long)
+        ulens = torch.zeros(B, dtype=torch.int32)
+        for i in range(B):
+            y = text_cpu[i][text_cpu[i] != self.ignore_id]
+            n = int(y.numel())
+            dec_in[i, 1:n + 1] = y
+            target[i, :n] = y
+            ulens[i] = n
+        dec_in_grad = dec_in.clone()
+        dec_in_grad[dec_in == self.decoder.blank_id] = -1
+        return {"dec_in": dec_in, "dec_in_grad": dec_in_grad, "rnnt_target": target, "rnnt_ulens": ulens}
 
     def _decoder_targets(self, text_cpu: torch.Tensor, tl_cpu: torch.Tensor, u_bucket: Optional[int]):
         """The decoder's (ys_in, ys_out, ys_in_lens) of a batch, on the host: add_sos_eos, padded to u_bucket + 1
@@ -339,6 +431,14 @@ class ESPnetASRModel(AbsESPnetModel):
     def _stats(self, loss, others, inter, detach: bool):
         """The reference's stats dict from the heads' (loss_ctc, loss_att, acc) and the intermediate branches'
         losses; detach: the values leave the autograd graph (forward_prepared's are autograd outputs)."""
+        if self.use_transducer_decoder:  # espnet_model.py:213-221, 264-269, 293: keys in the reference's order
+            stats = {}
+            if self.ctc is not None:
+                stats.update(loss_ctc=others[0:1], cer_ctc=None)
+            stats.update(loss_transducer=others[1:2], cer_transducer=None, wer_transducer=None, loss=loss)
+            if detach:
+                stats = {k: t if t is None else t.detach() for k, t in stats.items()}
+            return stats
         stats = dict(
             loss_ctc=others[0:1] if self.ctc is not None else None,
             cer_ctc=None,
@@ -369,7 +469,9 @@ class ESPnetASRModel(AbsESPnetModel):
             out4, _ = self._heads_forward(encoder_out, prep, Seeds(prep.heads_seed), False)
             loss, others = out4[3:4], out4[0:3]
         stats = self._stats(loss, others, inter, detach=True)
-        if not self.training and self.error_calculator is not None:
+        if not self.training and self.use_transducer_decoder:
+            stats.update(self._transducer_error_rates(encoder_out, prep))
+        elif not self.training and self.error_calculator is not None:
             stats.update(self._error_rates(encoder_out, prep))
         return loss, stats, d["weight"]
 
@@ -395,6 +497,20 @@ class ESPnetASRModel(AbsESPnetModel):
         saved, state = ctx
         dhs = self._heads_backward(state, g_loss, hook)
         self.encoder.run_backward(saved, dhs.contiguous(), hook)
+
+    def _transducer_error_rates(self, encoder_out, prep) -> Dict[str, Optional[torch.Tensor]]:
+        """Eval-mode cer_ctc (only when both report flags are off: the reference's quirk) and cer_transducer /
+        wer_transducer from the transducer beam search (espnet_model.py:525-540, 582-586)."""
+        dev = encoder_out.device
+        as_t = lambda v: None if v is None else torch.tensor([v], dtype=torch.float32, device=dev)
+        out = {}
+        if self.ctc is not None and self.error_calculator is not None:
+            ys_hat = self.ctc.argmax(encoder_out).cpu()
+            out["cer_ctc"] = as_t(self.error_calculator(ys_hat, prep.ys_pad_cpu, is_ctc=True))
+        if self.error_calculator_trans is not None:
+            cer, wer = self.error_calculator_trans(encoder_out, prep.host["rnnt_target"])
+            out["cer_transducer"], out["wer_transducer"] = as_t(cer), as_t(wer)
+        return out
 
     def _error_rates(self, encoder_out, prep) -> Dict[str, Optional[torch.Tensor]]:
         """Eval-mode error rates (espnet_model.py:515-521, 536-539): greedy CTC and decoder

@@ -7,8 +7,13 @@ Tokenizers: "bpe" (sentencepiece model file, as the SLURP recipes use) and "char
 ids2tokens by the model's token_list.  lm= (a TransformerLM, or an ESPnetLanguageModel whose .lm is used) adds
 neural-LM shallow fusion: scorer "lm" with weight lm_weight in the same weighted sum (and so in the "full" pre-beam
 key), as the reference's Speech2Text does with lm_train_config / lm_file / lm_weight (build the LM with
-tasks/lm.build_model and load_state_dict).  Word LM / n-gram / transducer / chunk-by-chunk encoding (the encoders'
-forward_infer) are out of scope.
+tasks/lm.build_model and load_state_dict).  Word LM / n-gram / chunk-by-chunk encoding (the encoders' forward_infer)
+are out of scope.
+
+A transducer model (asr_model.use_transducer_decoder) is searched by BeamSearchTransducer(decoder, joint_network,
+beam_size, **transducer_conf) (asr/transducer/beam_search_transducer.py: greedy at beam_size <= 1, else `default`);
+the results hold yseq[1:] (a transducer hypothesis has no trailing <eos>).  batch_search, streaming, an LM and
+decode_batch raise ValueError with such a model.
 
 batch_search=True runs the reference Speech2Text's own search instead, BatchBeamSearch (top `beam` over the
 flattened hypothesis x vocabulary scores, <eos> always CTC-scored), on the cached one-step decoder: the
@@ -53,13 +58,31 @@ class Speech2Text:
     def __init__(self, asr_model, token_list: Optional[List[str]] = None, beam_size: int = 20,
                  ctc_weight: float = 0.5, penalty: float = 0.0, nbest: int = 1, maxlenratio: float = 0.0,
                  minlenratio: float = 0.0, token_type: Optional[str] = None, bpemodel: Optional[str] = None,
-                 batch_search: bool = False, lm=None, lm_weight: float = 1.0, streaming: bool = False):
+                 batch_search: bool = False, lm=None, lm_weight: float = 1.0, streaming: bool = False,
+                 transducer_conf: Optional[dict] = None):
+        self.transducer = bool(getattr(asr_model, "use_transducer_decoder", False))
+        if self.transducer:
+            for name, on in (("batch_search", batch_search), ("streaming", streaming), ("lm", lm is not None)):
+                if on:
+                    raise ValueError(f"Speech2Text: {name} is not served with a transducer model")
+        elif transducer_conf is not None:
+            raise ValueError("Speech2Text: transducer_conf needs a transducer model (joint_network)")
         if streaming and lm is not None:
             raise ValueError("Speech2Text: streaming=True does not take an LM (the streaming search has no LM rollback)")
         asr_model.eval()
         self.asr_model = asr_model
         self.device = asr_model.flat.flat.device
         self.token_list = list(token_list if token_list is not None else asr_model.token_list)
+        self.maxlenratio, self.minlenratio, self.nbest = maxlenratio, minlenratio, nbest
+        self.streaming = streaming
+        self.tokenizer = (SentencepiecesTokenizer(bpemodel) if token_type == "bpe"
+                          else CharTokenizer() if token_type == "char" else None)
+        if self.transducer:
+            from ..asr.transducer.beam_search_transducer import BeamSearchTransducer
+            self.beam_search_transducer = BeamSearchTransducer(
+                decoder=asr_model.decoder, joint_network=asr_model.joint_network, beam_size=beam_size,
+                token_list=self.token_list, **(transducer_conf or {}))
+            return
         decoder = asr_model.decoder
         scorers = dict(decoder=DecoderScorer(decoder) if decoder is not None else None,
                        ctc=CTCPrefixScorer(asr_model.ctc, eos=asr_model.eos, blank=asr_model.blank_id),
@@ -74,7 +97,6 @@ class Speech2Text:
         self.batch_search = batch_search
         self.batch_beam_search = BatchBeamSearch(**kw)  # decode_batch's search, and __call__'s with batch_search
         self.beam_search = self.batch_beam_search if batch_search else BeamSearch(**kw)
-        self.streaming = streaming
         if streaming:
             self.beam_search = BatchBeamSearchOnlineSim(**kw)
             sizes = [getattr(asr_model.encoder, k, None) for k in ("block_size", "hop_size", "look_ahead")]
@@ -82,13 +104,6 @@ class Speech2Text:
                 self.beam_search.set_block_size(sizes[0])
                 self.beam_search.set_hop_size(sizes[1])
                 self.beam_search.set_look_ahead(sizes[2])
-        self.maxlenratio, self.minlenratio, self.nbest = maxlenratio, minlenratio, nbest
-        if token_type == "bpe":
-            self.tokenizer = SentencepiecesTokenizer(bpemodel)
-        elif token_type == "char":
-            self.tokenizer = CharTokenizer()
-        else:
-            self.tokenizer = None
 
     @torch.no_grad()
     def encode(self, speech: Union[torch.Tensor, np.ndarray]) -> torch.Tensor:
@@ -103,6 +118,8 @@ class Speech2Text:
     def __call__(self, speech: Union[torch.Tensor, np.ndarray]) -> List[Tuple[Optional[str], List[str], List[int],
                                                                                 Hypothesis]]:
         enc = self.encode(speech)
+        if self.transducer:
+            return self._results(self.beam_search_transducer(enc))
         return self._results(self.beam_search.forward(enc, self.maxlenratio, self.minlenratio))
 
     @torch.no_grad()
@@ -113,6 +130,8 @@ class Speech2Text:
         The padded-batch encode follows the reference's batch behaviour at utterance ends (the encoder treats a
         shorter utterance's padding as it does in a training batch), so its encoder outputs, and with them the
         scores, are not bit-equal to single-utterance encodes."""
+        if self.transducer:
+            raise ValueError("Speech2Text.decode_batch: decode_batch is not served with a transducer model")
         if self.streaming:
             raise ValueError("Speech2Text.decode_batch: the streaming search takes one utterance at a time")
         sp = [torch.as_tensor(s).to(torch.float32) for s in speeches]
@@ -128,7 +147,8 @@ class Speech2Text:
         hyps = hyps[: self.nbest]
         out = []
         for h in hyps:
-            token_int = [t for t in h.yseq[1:-1].tolist() if t != 0]
+            yseq = h.yseq[1:] if self.transducer else h.yseq[1:-1].tolist()
+            token_int = [t for t in yseq if t != 0]
             token = [self.token_list[i] for i in token_int]
             text = self.tokenizer.tokens2text(token) if self.tokenizer is not None else None
             out.append((text, token, token_int, h))

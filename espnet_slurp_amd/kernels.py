@@ -2034,3 +2034,98 @@ def conv2_dgrad(dz2, W, z1, dz1, B, T1, F1, D, dz2_16=None, z1bits=None):
         # algorithmic bytes (the whole entry): dz2 and W read, z1 (ReLU mask) read, dz1 written
         _PROF.append((2.0 * npix2 * 9 * D * D, ev0, ev1, (4, RC, B * T1 * F1, D, 9 * D, 1, "conv2_dgrad"),
                       4.0 * (npix2 * D + 9 * D * D + 2 * B * T1 * F1 * D)))
+
+
+# ----------------------------------------------------------------------------- RNN-Transducer head
+RNNT_ACT = {"tanh": 0, "relu": 1}
+
+
+def rnnt_act(name: str) -> int:
+    """The joint activation's kernel code; any other espnet2 joint_activation_type raises by name."""
+    if name not in RNNT_ACT:
+        raise NotImplementedError(f"joint_activation_type={name}: the joint kernels serve {sorted(RNNT_ACT)}")
+    return RNNT_ACT[name]
+
+
+def rnnt_joint_fwd(pe, pd, z, B, T, U1, J, act):
+    """z (B, T, U1, J) = act(pe[b,t,:] + pd[b,u,:])."""
+    _f32(pe, pd, z)
+    assert pe.numel() == B * T * J and pd.numel() == B * U1 * J and z.numel() == B * T * U1 * J
+    _native.call("esp_rnnt_joint_fwd", _p(pe), _p(pd), _p(z), B, T, U1, J, act, _st())
+    return z
+
+
+def rnnt_joint_bwd(dz, z, hlens_i32, tlens_i32, dpe, dpd, B, T, U1, J, act):
+    """dpe[b,t,:] = sum_u dz act'(z), dpd[b,u,:] = sum_t dz act'(z) over the valid cells (fixed order)."""
+    _f32(dz, z, dpe, dpd)
+    assert dz.numel() == z.numel() == B * T * U1 * J and dpe.numel() == B * T * J and dpd.numel() == B * U1 * J
+    n = _wsize("esp_rnnt_joint_bwd", B, T, U1, J)
+    w = _ws(WS, "esp_rnnt_joint_bwd", n, dz.device)
+    _native.call("esp_rnnt_joint_bwd", _p(dz), _p(z), _p(hlens_i32), _p(tlens_i32), _p(dpe), _p(dpd), B, T, U1, J,
+                 act, _p(w), n, _st())
+    _guard_post("esp_rnnt_joint_bwd", w, n)
+
+
+def rnnt_workspace(B, T, U1, device) -> torch.Tensor:
+    """The lattice's fp64 workspace (lse | lp_blank | lp_y | alpha | beta, each (B, T, U1)): the caller owns it,
+    because the gradient kernel reads in the backward what the forward wrote."""
+    return torch.empty(_wsize("esp_rnnt_loss", B, T, U1) // 8, dtype=torch.float64, device=device)
+
+
+def _rnnt_check(logits, ys, work, B, T, U1, V):
+    _f32(logits)
+    _need_f64(work)
+    assert logits.numel() == B * T * U1 * V and logits.is_contiguous(), (tuple(logits.shape), B, T, U1, V)
+    assert ys.dtype == torch.int64 and ys.numel() == B * (U1 - 1), (ys.dtype, tuple(ys.shape), B, U1)
+
+
+def rnnt_logprobs(logits, ys, hlens_i32, tlens_i32, B, T, U1, V, work):
+    _rnnt_check(logits, ys, work, B, T, U1, V)
+    _native.call("esp_rnnt_logprobs", _p(logits), _p(ys), _p(hlens_i32), _p(tlens_i32), B, T, U1, V, _p(work),
+                 work.numel() * 8, _st())
+
+
+def rnnt_alpha_beta(hlens_i32, tlens_i32, B, T, U1, work, nll):
+    _need_f64(work, nll)
+    _native.call("esp_rnnt_alpha_beta", _p(hlens_i32), _p(tlens_i32), B, T, U1, _p(work), work.numel() * 8, _p(nll),
+                 _st())
+
+
+def rnnt_grad(logits, ys, hlens_i32, tlens_i32, B, T, U1, V, gscale, nll, work, gdev=None):
+    """logits <- gscale * (gdev ? *gdev : 1) * d(sum_b nll_b)/d logits, in place."""
+    _rnnt_check(logits, ys, work, B, T, U1, V)
+    _need_f64(nll)
+    _f32(gdev)
+    _native.call("esp_rnnt_grad", _p(logits), _p(ys), _p(hlens_i32), _p(tlens_i32), B, T, U1, V, float(gscale),
+                 _p(gdev), _p(nll), _p(work), work.numel() * 8, _st())
+    return logits
+
+
+def _pitch(t, width):
+    assert t.stride(-1) == 1 and t.shape[-1] == width and t.dim() == 2, (tuple(t.shape), t.stride(), width)
+    return t.stride(0)
+
+
+def lstm_cell_fwd(xproj, hprev, cprev, Whh, acts, hout, hout2, cout):
+    """One LSTM step for B rows: every operand a (B, .) view with unit inner stride (rows of a sequence buffer);
+    hprev / cprev None: zero state; acts / hout2 None: not written."""
+    B, H = hout.shape
+    _f32(xproj, hprev, cprev, Whh, acts, hout, hout2, cout)
+    assert Whh.shape == (4 * H, H) and Whh.is_contiguous()
+    _native.call("esp_lstm_cell_fwd", _p(xproj), _pitch(xproj, 4 * H), _p(hprev), _pitch(hprev, H) if hprev is not None else 0,
+                 _p(cprev), _pitch(cprev, H) if cprev is not None else 0, _p(Whh), _p(acts),
+                 _pitch(acts, 4 * H) if acts is not None else 0, _p(hout), _pitch(hout, H), _p(hout2),
+                 _pitch(hout2, H) if hout2 is not None else 0, _p(cout), _pitch(cout, H), B, H, _st())
+
+
+def lstm_cell_bwd(dh, dgnext, Whh, acts, c, cprev, dc_in, dc_out, dgates):
+    """The backward of one LSTM step: dgates (B, 4H view) <- pre-activation gate gradients, dc_out (B, H contiguous)
+    <- the cell gradient carried to step u - 1; dgnext / cprev / dc_in None at the sequence ends."""
+    B, H = dh.shape
+    _f32(dh, dgnext, Whh, acts, c, cprev, dc_in, dc_out, dgates)
+    assert Whh.shape == (4 * H, H) and Whh.is_contiguous() and dc_out.is_contiguous() and dc_out.shape == (B, H)
+    assert dc_in is None or (dc_in.is_contiguous() and dc_in.shape == (B, H))
+    _native.call("esp_lstm_cell_bwd", _p(dh), _pitch(dh, H), _p(dgnext), _pitch(dgnext, 4 * H) if dgnext is not None else 0,
+                 _p(Whh), _p(acts), _pitch(acts, 4 * H), _p(c), _pitch(c, H), _p(cprev),
+                 _pitch(cprev, H) if cprev is not None else 0, _p(dc_in), _p(dc_out), _p(dgates), _pitch(dgates, 4 * H),
+                 B, H, _st())

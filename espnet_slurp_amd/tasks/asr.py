@@ -11,6 +11,7 @@ import torch
 
 from ..asr.ctc import CTC
 from ..asr.decoder.mlm_decoder import MLMDecoder
+from ..asr.decoder.transducer_decoder import TransducerDecoder
 from ..asr.decoder.transformer_decoder import TransformerDecoder
 from ..asr.encoder.branchformer_encoder import BranchformerEncoder
 from ..asr.encoder.conformer_encoder import ConformerEncoder
@@ -20,6 +21,7 @@ from ..asr.encoder.transformer_encoder import TransformerEncoder
 from ..asr.espnet_model import ESPnetASRModel
 from ..asr.maskctc_model import MaskCTCModel
 from ..asr.specaug.specaug import SpecAug
+from ..asr.transducer.joint_network import JointNetwork
 from ..asr.frontend.default import DefaultFrontend
 from ..layers.global_mvn import GlobalMVN
 from ..layers.utterance_mvn import UtteranceMVN
@@ -61,7 +63,8 @@ encoder_choices = ClassChoices("encoder", dict(conformer=ConformerEncoder, trans
 # tests/test_branchformer_cpu.py hold it to exactly those and to rejecting every other name): a second registry of
 # the same kind, which `encoder_class` -- and through it build_model -- reads first.  The two belong in one table.
 added_encoder_choices = ClassChoices("encoder", dict(e_branchformer=EBranchformerEncoder), default=None)
-decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder, mlm=MLMDecoder), default="rnn",
+decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder, mlm=MLMDecoder,
+                                                       transducer=TransducerDecoder), default="rnn",
                                optional=True)
 
 
@@ -79,7 +82,7 @@ def build_model(args: argparse.Namespace, device="cuda") -> ESPnetASRModel:
     """ASRTask.build_model (asr.py:439-562) for the fbank (--input_size) path.
 
     args needs: token_list (a list or a token file path, as asr.py:441-450), input_size,
-    specaug/_conf, normalize/_conf, encoder/_conf, decoder/_conf, ctc_conf, model_conf, init
+    specaug/_conf, normalize/_conf, encoder/_conf, decoder/_conf, joint_net_conf, ctc_conf, model_conf, init
     (the resolved config.yaml fields)."""
     if isinstance(args.token_list, str):
         with open(args.token_list, encoding="utf-8") as f:
@@ -92,8 +95,6 @@ def build_model(args: argparse.Namespace, device="cuda") -> ESPnetASRModel:
     for opt in ("preencoder", "postencoder"):
         if getattr(args, opt, None) is not None:
             raise NotImplementedError(f"--{opt}: not on the Conformer CTC/attention hot path")
-    if getattr(args, "decoder", None) == "transducer":
-        raise NotImplementedError("--decoder transducer: not on the CTC/attention hot path")
     vocab_size = len(token_list)
     if getattr(args, "input_size", None) is None:  # extract features in the model (asr.py:459-468)
         frontend = frontend_choices.get_class(getattr(args, "frontend", "default"))(
@@ -109,12 +110,18 @@ def build_model(args: argparse.Namespace, device="cuda") -> ESPnetASRModel:
     normalize = norm_cls(**(getattr(args, "normalize_conf", None) or {})) if norm_cls else None
     encoder = encoder_class(args.encoder)(input_size=input_size, **(args.encoder_conf or {}))
     dec_cls = decoder_choices.get_class(getattr(args, "decoder", None))
-    decoder = dec_cls(vocab_size=vocab_size, encoder_output_size=encoder.output_size(),
-                      **(getattr(args, "decoder_conf", None) or {})) if dec_cls else None
+    joint_network = None
+    if getattr(args, "decoder", None) == "transducer":  # asr.py:509-521
+        decoder = dec_cls(vocab_size, embed_pad=0, **(getattr(args, "decoder_conf", None) or {}))
+        joint_network = JointNetwork(vocab_size, encoder.output_size(), decoder.dunits,
+                                     **(getattr(args, "joint_net_conf", None) or {}))
+    else:
+        decoder = dec_cls(vocab_size=vocab_size, encoder_output_size=encoder.output_size(),
+                          **(getattr(args, "decoder_conf", None) or {})) if dec_cls else None
     ctc = CTC(odim=vocab_size, encoder_output_size=encoder.output_size(), **(getattr(args, "ctc_conf", None) or {}))
     model_cls = model_choices.get_class(getattr(args, "model", "espnet"))
     model = model_cls(vocab_size=vocab_size, frontend=frontend, specaug=specaug, normalize=normalize, preencoder=None,
-                      encoder=encoder, postencoder=None, decoder=decoder, ctc=ctc, joint_network=None,
+                      encoder=encoder, postencoder=None, decoder=decoder, ctc=ctc, joint_network=joint_network,
                       token_list=token_list, **(getattr(args, "model_conf", None) or {}))
     if getattr(args, "init", None) is not None:  # asr.py:556-557
         initialize(model, args.init)

@@ -709,6 +709,56 @@ int esp_lm_front_bwd(const float* dy, const float* x, const float* gamma, const 
  * does not call it (the features are data); an encoder's run_backward forms it on request. */
 int esp_conv1_dgrad(const float* dz1, const float* W, float* dx, int B, int T, int F, int D, void* stream);
 
+/* ---- RNN-Transducer head (additive: no signature above changed).  espnet2/asr/espnet_model.py:542-588,
+ * espnet2/asr_transducer/joint_network.py, espnet2/asr/decoder/transducer_decoder.py.  Lengths are device int32
+ * arrays (hlens[b] = T_b frames, tlens[b] = U_b labels, clamped to the padded extents T and U1 - 1); blank is
+ * token 0; U1 = Umax + 1 <= 1024 and B*T*U1 < 2^31, else status -1.
+ *
+ * esp_rnnt_joint_fwd (csrc/rnnt.hip): z (B, T, U1, J) = act(pe[b,t,:] + pd[b,u,:]), pe (B*T, J), pd (B*U1, J);
+ * act 0 tanh, 1 relu; every cell of the padded extent is written.
+ * esp_rnnt_joint_bwd: dz (B, T, U1, J) and the forward's z -> dpe[b,t,:] = sum_u dz act'(z), dpd[b,u,:] = sum_t
+ * dz act'(z), every element written.  Cells with t >= T_b or u > U_b are not read and add exactly zero.  Fixed
+ * summation order, no atomics (per-tile partials in `work`, then a reduce pass): bit-reproducible.
+ *
+ * The loss shares one fp64 workspace of esp_rnnt_loss_workspace_bytes(B, T, U1) = 5 B T U1 doubles: lse | lp_blank
+ * | lp_y | alpha | beta, each (B, T, U1).
+ * esp_rnnt_logprobs: logits (B*T*U1, V) fp32, any V >= 1; ys (B, U1 - 1) int64.  Per valid cell the max-shifted
+ * log-sum-exp over V, the blank log-probability and (u < U_b) that of label ys[b,u]; padded cells: unread, zeros
+ * in all five arrays.
+ * esp_rnnt_alpha_beta: the lattice recursions, one workgroup per (utterance, direction), anti-diagonal sweep, fp64:
+ * alpha[0,0] = 0, alpha[t,u] = lse(alpha[t-1,u] + lp_blank[t-1,u], alpha[t,u-1] + lp_y[t,u-1]); beta[T_b-1,U_b] =
+ * lp_blank[T_b-1,U_b], beta[t,u] = lse(beta[t+1,u] + lp_blank[t,u], beta[t,u+1] + lp_y[t,u]); nll[b] =
+ * -(alpha[T_b-1,U_b] + lp_blank[T_b-1,U_b]) (fp64; +inf when T_b <= 0).  Any T_b >= 1, U_b >= 0.
+ * esp_rnnt_grad: overwrites the logits with the gradient of gscale * (gdev ? *gdev : 1) * sum_b nll_b w.r.t. them
+ * (gdev: an optional device float, e.g. the upstream gradient of the loss); padded cells and utterances with a
+ * non-finite nll: exactly 0. */
+int esp_rnnt_joint_fwd(const float* pe, const float* pd, float* z, int B, int T, int U1, int J, int act, void* stream);
+int esp_rnnt_joint_bwd(const float* dz, const float* z, const int* hlens, const int* tlens, float* dpe, float* dpd,
+                       int B, int T, int U1, int J, int act, float* work, long work_bytes, void* stream);
+int esp_rnnt_logprobs(const float* logits, const long long* ys, const int* hlens, const int* tlens, int B, int T,
+                      int U1, int V, double* work, long work_bytes, void* stream);
+int esp_rnnt_alpha_beta(const int* hlens, const int* tlens, int B, int T, int U1, double* work, long work_bytes,
+                        double* nll, void* stream);
+int esp_rnnt_grad(float* logits, const long long* ys, const int* hlens, const int* tlens, int B, int T, int U1, int V,
+                  float gscale, const float* gdev, const double* nll, const double* work, long work_bytes,
+                  void* stream);
+
+/* esp_lstm_cell_fwd / _bwd (csrc/lstm.hip): one time step of a torch.nn.LSTM layer (gates i, f, g, o) for B rows of
+ * H units, any H >= 1; every matrix is addressed by a pointer and a row pitch in floats, so a step reads and writes
+ * slices of (B, U1, .) sequence buffers in place.  xproj: x W_ih^T + b_ih + b_hh of this step (4H per row).  The
+ * forward adds hprev W_hh^T (W_hh (4H, H); exact fp32 FMA, fixed order; hprev / cprev NULL: zero state), writes the
+ * gate activations to acts (4H per row; NULL: not kept), c to cout and h to hout and, when given, hout2.  The backward
+ * takes dh (the gradient of h_u from above), dgnext (the pre-activation gate gradients of step u + 1, NULL at the last
+ * step: the recurrent part dgnext W_hh is added inside), dc_in (B, H; the cell gradient carried from step u + 1, NULL:
+ * zero) and writes dgates (4H per row; the gradient of xproj and of the recurrent product) and dc_out (B, H; may be
+ * dc_in).  One launch per step. */
+int esp_lstm_cell_fwd(const float* xproj, long ldx, const float* hprev, long ldh, const float* cprev, long ldc,
+                      const float* Whh, float* acts, long lda, float* hout, long ldho, float* hout2, long ldho2,
+                      float* cout, long ldco, int B, int H, void* stream);
+int esp_lstm_cell_bwd(const float* dh, long lddh, const float* dgnext, long ldgn, const float* Whh, const float* acts,
+                      long lda, const float* c, long ldc, const float* cprev, long ldcp, const float* dc_in,
+                      float* dc_out, float* dgates, long ldg, int B, int H, void* stream);
+
 /* ---- workspace sizes.  Every launcher that takes a scratch `work` buffer also takes its size
  * in bytes and fails (status -1, esp_last_error) when it is smaller than the size below, which is
  * computed by the same code that picks the launcher's chunking: callers size their buffers from
@@ -723,6 +773,8 @@ long esp_bn_swish_bwd_workspace_bytes(int M, int D);
 long esp_conv1_wgrad_workspace_bytes(int B, int T, int F, int D);
 long esp_conv2_dgrad_workspace_bytes(int D);
 long esp_ctc_loss_workspace_bytes(int B, int T, int Umax);
+long esp_rnnt_joint_bwd_workspace_bytes(int B, int T, int U1, int J);
+long esp_rnnt_loss_workspace_bytes(int B, int T, int U1);
 /* esp_relpos_dp adapts its grouping to the buffer it gets; this is its preferred size */
 long esp_relpos_dp_workspace_bytes(int nb, int H, int T);
 
