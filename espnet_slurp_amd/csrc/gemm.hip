@@ -127,7 +127,7 @@ int g_last_grid = 0;  // the grid of the last LDS-DMA launch (EPI_C1FOLD: its pe
 int g_splitk = 0;
 int splitk_mode() { return g_splitk; }
 
-// gemm_wgrad_ws_kernel for the eligible RC x RC fp32 GEMMs: 0 never, 1 when its split-K grid fills the chip
+// gemm_wgrad_ws_kernel for the eligible RC x RC / RC x I2C_RC fp32 GEMMs: 0 never, 1 when its split-K grid fills the chip
 // (default), 2 whenever the launch is structurally eligible (tests: small shapes)
 int g_wgrad_ws = 1;
 
@@ -165,8 +165,7 @@ bool launch_glds(int MA, int MB, const GemmArgs& g, int batch, hipStream_t st, c
   // implicit-im2col B: pixel offsets on 24-bit multiplies (i2c_pix_off24)
   if (MB == I2C_RC) {
     const long kpix = g.bf16 == 2 ? 2L * g.K : (long)g.K;  // (bf16: K counts pixel pairs)
-    const long rows = kpix / ((long)g.b.ic.Ho * g.b.ic.Wo) * g.b.ic.H * g.b.ic.W;  // Bn * H * W
-    if (rows >= (1L << 24) || rows * g.b.ic.C >= (1L << 32)) return false;
+    if (!i2c_rc_off24_ok(g.b.ic, kpix)) return false;
   }
   int kind = g.splits > 1 ? EPI_PLAIN : epi_kind_spec(g);
   if (g.cpn) {  // planes output: only its specialised kinds, no fallback kind
@@ -209,7 +208,7 @@ bool launch_glds(int MA, int MB, const GemmArgs& g, int batch, hipStream_t st, c
   x.fd_splits = make_fastdiv((uint32_t)g.splits);
   x.fd_nb2 = make_fastdiv((uint32_t)g.nb2);
   const int prec = g.bf16;
-  if (g.ws) return kind == EPI_PLAIN && wgrad_ws_launch(rs, grid, st, g, x);
+  if (g.ws) return kind == EPI_PLAIN && wgrad_ws_launch(MB == I2C_RC, rs, grid, st, g, x);
   if (kind == EPI_PLAIN) return glds_launch_plain(MA, MB, BNT, prec, rs, grid, st, g, x);
   if (kind == EPI_FWD || kind == EPI_BWD) return glds_launch_epi(MA, MB, BNT, prec, kind, grid, st, g, x);
   if (kind == EPI_P0 || kind == EPI_PR || kind == EPI_SMB || kind == EPI_SMBN || kind == EPI_P0_PL)
@@ -753,9 +752,14 @@ static int gemm_run(int mode_a, int mode_b, int M, int N, int K, int batch, int 
   // times -- and its 128 KB partial store stay a small share of its k-loop; the d x d gradients over the decoder's
   // few thousand tokens keep 128-row tiles: the splits cannot refill the chip there); an unsplit launch without
   // row sums keeps the specialised plain kinds (EPI_P0 / EPI_PR) of gemm_glds_kernel.
+  // The conv2 weight gradient (RC x I2C_RC: B gathered from the conv1 map) takes the same kernel with the gather
+  // on its producer waves, under the same conditions plus those of the gather itself: C % 4 == 0 (a 16-byte quad
+  // of im2col columns stays inside one tap) and the 24-bit pixel decode's limits (i2c_rc_off24_ok).
   constexpr int kWsMinChunk = 16 * GL_BK;
   bool ws = false;
-  if (ESP_WGRAD_WS && ESP_F32_SPLIT && g_wgrad_ws && mode_a == RC && mode_b == RC && g.bf16 == 0 && prec_in < 0 && batch == 1 &&
+  const bool ws_b = mode_b == RC || (mode_b == I2C_RC && K > 0 && g.b.ic.C % 4 == 0 && g.b.ic.Ho > 0 && g.b.ic.Wo > 0 &&
+                                     i2c_rc_off24_ok(g.b.ic, K));
+  if (ESP_WGRAD_WS && ESP_F32_SPLIT && g_wgrad_ws && mode_a == RC && ws_b && g.bf16 == 0 && prec_in < 0 && batch == 1 &&
       g.bnt && !cpn && !smb && !band && M % 4 == 0 && N % 4 == 0 && M >= 4 && N >= 4 && K > 0 && !bias && !aux && !act &&
       !bwd_act && drop_p == 0.f && (g_wgrad_ws == 2 || M >= 256)) {  // (M = 256: the narrowest Linear here)
     const int bnt0 = g.bnt, bm0 = g.bm;

@@ -18,8 +18,9 @@
 // 4 waves (2x2), each wave 64x64 = 2x2 MFMA 32x32 tiles.  A lane of half h uses k = 16h+s, s = 0..15, of a
 // slab (both operands agree); see Stage / StageS / StageP and frag16 / frag_pl_* for the LDS images.
 // Global->LDS is LDS-DMA (global_load_lds_dwordx4) into a 2-slab ring: the next slab streams in while the
-// current slab's fragments are read.  The Linear weight gradients (RC x RC, fp32) have a kernel of their own
-// with the operand split on dedicated waves: gemm_wgrad_ws.hip.
+// current slab's fragments are read.  The fp32 weight gradients (RC x RC: the Linears; RC x I2C_RC: conv2, B
+// gathered from the conv1 map) have a kernel of their own with the operand split on dedicated waves:
+// gemm_wgrad_ws.hip.
 // Epilogue (fused): bias, ReLU/Swish (pre-activation optionally stored to `aux`),
 // counter-RNG dropout, alpha scale and beta*R residual.
 #include <stdlib.h>
@@ -49,8 +50,8 @@ constexpr int BM = 128, BN = 128, BK = 32, NT = 256;  // BK: split-K granularity
 #ifndef ESP_GEMM_PIPE
 #define ESP_GEMM_PIPE 1
 #endif
-// 1 (default): the eligible fp32 RC x RC GEMMs (Linear weight gradients) run gemm_wgrad_ws_kernel
-// (gemm_wgrad_ws.hip: split once per block on producer waves); 0: gemm_glds_kernel as before (an A/B build:
+// 1 (default): the eligible fp32 RC x RC and RC x I2C_RC GEMMs (Linear and conv2 weight gradients) run
+// gemm_wgrad_ws_kernel (gemm_wgrad_ws.hip: split once per block on producer waves); 0: gemm_glds_kernel (an A/B build:
 // make VARIANT=_nows EXTRA=-DESP_WGRAD_WS=0)
 #ifndef ESP_WGRAD_WS
 #define ESP_WGRAD_WS 1
@@ -122,7 +123,7 @@ struct GemmArgs {
              // three bf16 split planes (esp_gemm_f32_bp: B's ld, strides, ps in bf16 elements)
   int bnt;  // LDS-DMA kernel tile width (128, or 64 for narrow / mid-size grids); 0 = fallback kernel
   int bm;   // LDS-DMA kernel tile height: 128, or 64 (with bnt 64) for under-filled grids
-  int ws;   // 1: gemm_wgrad_ws_kernel (bm WGRAD_WS_BM, bnt 128; RC x RC, PREC 0, plain epilogue; one block per CU)
+  int ws;   // 1: gemm_wgrad_ws_kernel (bm WGRAD_WS_BM, bnt 128; RC x RC / I2C_RC, PREC 0, plain epilogue; one block per CU)
   int bwd_act;       // != 0: backward epilogue  v = drop'(acc) * act'(pre)  (act code, dropout regenerated)
   const float* pre;  // pre-activation (same layout as C) for bwd_act
   float* rowsum;     // != NULL: rowsum[m] += sum_k A(m,k)  (bias gradient of a weight-gradient GEMM)
@@ -2530,8 +2531,15 @@ bool glds_launch_spec(int ma, int mb, int bnt, int prec, int epi, dim3 grid, hip
                       const GldsArgs& x);
 bool glds_launch_pspec(int ma, int mb, int bnt, int prec, int epi, dim3 grid, hipStream_t st, const GemmArgs& g,
                        const GldsArgs& x);
-// gemm_wgrad_ws.hip: the launch of gemm_wgrad_ws_kernel (g.ws; false: not built, ESP_WGRAD_WS=0)
-bool wgrad_ws_launch(bool rs, dim3 grid, hipStream_t st, const GemmArgs& g, const GldsArgs& x);
+// gemm_wgrad_ws.hip: the launch of gemm_wgrad_ws_kernel (g.ws; false: not built, ESP_WGRAD_WS=0); gather_b: B is
+// an I2C_RC operand (x.c_b / hw_b / wo_b set), else RC
+bool wgrad_ws_launch(bool gather_b, bool rs, dim3 grid, hipStream_t st, const GemmArgs& g, const GldsArgs& x);
+// an I2C_RC operand's pixel offsets fit i2c_pix_off24: Bn * H * W < 2^24 and the map < 2^32 elements (kpix: the
+// number of output pixels)
+inline bool i2c_rc_off24_ok(const Im2col& ic, long kpix) {
+  const long rows = kpix / ((long)ic.Ho * ic.Wo) * ic.H * ic.W;  // Bn * H * W
+  return rows < (1L << 24) && rows * ic.C < (1L << 32);
+}
 // resident blocks per CU of a launch (host side)
 inline int glds_occupancy_rt(int bnt, int epi, int bm, int prec) {
   const int by_regs = bm == 256 ? 1 : bm == 64 ? 4 : (bnt == 64 && (epi == EPI_PLAIN || epi >= EPI_BIAS)) ? 3 : 2;

@@ -1,5 +1,16 @@
-// gemm_wgrad_ws_kernel: the fp32 (PREC 0, split-product) RC x RC GEMM of the Linear weight gradients
-// (dW += dy^T x, bias gradient fused), with the operand split done ONCE per block on dedicated waves.
+// gemm_wgrad_ws_kernel: the fp32 (PREC 0, split-product) weight-gradient GEMMs with the operand split done ONCE
+// per block on dedicated waves: RC x RC, the Linear weight gradients (dW += dy^T x, bias gradient fused), and
+// RC x I2C_RC (GB), the conv2 weight gradient dW2r = dz2^T im2col(z1) with B gathered from the NHWC conv1 map.
+//
+// The gathered B (GB, a compile-time parameter: the RC x RC instantiations are unchanged): a tile row is a column
+// (kt, kf, c) of the im2col view and a k-row an output pixel, so a producer lane's 16-byte quad -- four channels
+// of one tap, C % 4 == 0 -- sits at the same offset from every pixel's receptive-field origin.  That offset
+// (i2c_col_off) goes into the lane's base pointer once per tile; each of the lane's four loads per slab decodes
+// its own pixel's origin (i2c_pix_off24: two multiply-high divisions and 24-bit multiplies, no branch), the only
+// VALU the gather adds.  One 256 x 128 tile covers all of M = D = 256, so every B slab is gathered once per column
+// tile (the 128-row kernel fetched it once per row tile) and split once.  Everything after the load -- the plane
+// image, the ring, the barrier schedule, the consumers -- is the RC x RC kernel's, so an unsplit launch gives the C of
+// gemm_glds_kernel<RC, I2C_RC, ., ., EPI_PLAIN, 0> bit for bit.
 //
 // One 512-thread block per CU, tile BMT x 128, two roles:
 //   producers (waves 4-7; VALU + memory only): fetch the A and B slabs (32 k-rows x tile rows) with 16-byte
@@ -55,11 +66,26 @@ struct WsStage {
     const int c = LQ * pw + (lane % LQ);
     p = base + min(row0 + 4 * c, rows - 4);  // rows % 4 == 0, rows >= 4 (host)
   }
+  // the gathered form (I2C_RC: a tile row is a column (kt, kf, c) of the im2col view of an NHWC map, a k-row an
+  // output pixel): the quad's column offset from the receptive-field origin is the same at every k-row (C % 4 == 0
+  // keeps a quad inside one tap), so it is folded into p once per tile
+  __device__ __forceinline__ void init_tile_i2c(const Operand& op, const FastDiv& fc, int rows, int row0, int pw,
+                                                int lane) {
+    const int c = LQ * pw + (lane % LQ);
+    p = op.p + i2c_col_off(op.ic, fc, min(row0 + 4 * c, rows - 4));
+  }
   // load i of the slab at k0; k-rows past K read the last one (finite in-range values, as the LDS-DMA staging
   // clamps them)
   __device__ __forceinline__ float4 load(long ld, int K, int k0, int i) const {
     const int k = min(k0 + KP * i + krl, K - 1);
     return *reinterpret_cast<const float4*>(p + (long)k * ld);
+  }
+  // ... gathered: the pixel's receptive-field origin, decoded per load on 24-bit multiplies (host: Bn H W < 2^24,
+  // the map < 2^32 elements) and added as an unsigned 32-bit element offset to the 64-bit pointer
+  __device__ __forceinline__ float4 load_i2c(const Operand& op, const FastDiv& fhw, const FastDiv& fwo, int K, int k0,
+                                             int i) const {
+    const uint32_t k = (uint32_t)min(k0 + KP * i + krl, K - 1);
+    return *reinterpret_cast<const float4*>(p + i2c_pix_off24(op.ic, fhw, fwo, k));
   }
   // split load i's values and write the planes; ZERO (operand A): k-rows >= kv are written as zeros; RS: rs += the
   // values
@@ -84,7 +110,8 @@ struct WsStage {
   }
 };
 
-template <int BMT, bool RS>
+// GB: B gathered from an NHWC map (I2C_RC) instead of read as a row-major [K][N] matrix (RC)
+template <int BMT, bool RS, bool GB>
 __global__ __launch_bounds__(WS_NT, 1) void gemm_wgrad_ws_kernel(GemmArgs g, GldsArgs x) {
   static_assert(BMT == 256 || BMT == 128, "tile height");
   constexpr int TM = BMT / 64, TN = 2;                // a consumer wave: BMT / 2 x 64
@@ -121,13 +148,17 @@ __global__ __launch_bounds__(WS_NT, 1) void gemm_wgrad_ws_kernel(GemmArgs g, Gld
     if (!lok) return;
     if (lkt == 0) {
       sa.init_tile(g.a.p, g.M, lc.m0, pw, lane);
-      sb.init_tile(g.b.p, g.N, lc.n0, pw, lane);
+      if constexpr (GB) sb.init_tile_i2c(g.b, x.c_b, g.N, lc.n0, pw, lane);
+      else sb.init_tile(g.b.p, g.N, lc.n0, pw, lane);
     }
     const int k0 = lc.kbeg + lkt * GL_BK;
 #pragma unroll
     for (int i = 0; i < NIA; ++i) va[i] = sa.load(g.a.ld, g.K, k0, i);
 #pragma unroll
-    for (int i = 0; i < NIB; ++i) vb[i] = sb.load(g.b.ld, g.K, k0, i);
+    for (int i = 0; i < NIB; ++i) {
+      if constexpr (GB) vb[i] = sb.load_i2c(g.b, x.hw_b, x.wo_b, g.K, k0, i);
+      else vb[i] = sb.load(g.b.ld, g.K, k0, i);
+    }
     held_kv = lc.kend - k0;
     held_rs = RS && lc.tn == 0;
     if (++lkt == lc.nk) {
@@ -267,16 +298,22 @@ __global__ __launch_bounds__(WS_NT, 1) void gemm_wgrad_ws_kernel(GemmArgs g, Gld
 
 }  // namespace
 
-bool wgrad_ws_launch(bool rs, dim3 grid, hipStream_t st, const GemmArgs& g, const GldsArgs& x) {
+bool wgrad_ws_launch(bool gather_b, bool rs, dim3 grid, hipStream_t st, const GemmArgs& g, const GldsArgs& x) {
   if (g.bm != WGRAD_WS_BM || g.bnt != WS_BN) return false;
-  if (rs) hipLaunchKernelGGL((gemm_wgrad_ws_kernel<WGRAD_WS_BM, true>), grid, dim3(WS_NT), 0, st, g, x);
-  else hipLaunchKernelGGL((gemm_wgrad_ws_kernel<WGRAD_WS_BM, false>), grid, dim3(WS_NT), 0, st, g, x);
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(WS_NT), 0, st, g, x); };
+  if (gather_b) {
+    if (rs) go(gemm_wgrad_ws_kernel<WGRAD_WS_BM, true, true>);
+    else go(gemm_wgrad_ws_kernel<WGRAD_WS_BM, false, true>);
+  } else {
+    if (rs) go(gemm_wgrad_ws_kernel<WGRAD_WS_BM, true, false>);
+    else go(gemm_wgrad_ws_kernel<WGRAD_WS_BM, false, false>);
+  }
   return true;
 }
 
 #else
 
-bool wgrad_ws_launch(bool, dim3, hipStream_t, const GemmArgs&, const GldsArgs&) { return false; }
+bool wgrad_ws_launch(bool, bool, dim3, hipStream_t, const GemmArgs&, const GldsArgs&) { return false; }
 
 #endif
 

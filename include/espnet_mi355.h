@@ -78,7 +78,10 @@ int esp_set_splitk_mode(int mode);
  * waves) when M >= 256 and K is long enough for its split-K grid to fill the chip; 2 = that kernel for every
  * structurally eligible launch (unbatched, M % 4 == N % 4 == 0, LDS-DMA-eligible operands, split K or row sums);
  * 0 = never (the 128-row LDS-DMA kernel, as in a build with ESP_WGRAD_WS=0, where this call changes nothing).
- * Unsplit, both kernels give the same C bit for bit.  Returns the previous mode. */
+ * Unsplit, both kernels give the same C bit for bit.  The same switch, with the same meaning, covers the fp32
+ * RC x I2C_RC GEMM (the conv2 weight gradient, B gathered from the NHWC conv1 map on the producer waves) when C % 4
+ * == 0, Bn * H * W < 2^24 and the map holds < 2^32 elements; esp_conv2_wgrad_bf16 is not affected.  Returns the
+ * previous mode. */
 int esp_set_wgrad_ws(int mode);
 /* esp_gemm_f32 with B also given as its three bf16 split planes (esp_f32_to_planes of the fp32 B,
  * b = hi + mid + lo exactly): the same fp32 split products as esp_gemm_f32 on the fp32 B, in the same

@@ -28,9 +28,12 @@ def per_dispatch(d, counter):
 def main():
     fetch = per_dispatch(sys.argv[1], "FETCH_SIZE")
     write = per_dispatch(sys.argv[2], "WRITE_SIZE")
-    fam = "gemm_glds_kernel"  # the fp32 / bf16-in-LDS and the bf16-operand GEMMs are all this template
-    fk = [v for n, v in fetch.values() if fam in n]
-    wk = [v for n, v in write.values() if fam in n]
+    # the fp32 / bf16-in-LDS and the bf16-operand GEMMs are all the first template; the weight gradients with the
+    # operand split on producer waves (Linear and conv2) are the second
+    fams = ("gemm_glds_kernel", "gemm_wgrad_ws_kernel")
+    fam = " + ".join(fams)
+    fk = [v for n, v in fetch.values() if any(f in n for f in fams)]
+    wk = [v for n, v in write.values() if any(f in n for f in fams)]
     fetch_b = 2.0 * 1024 * sum(fk) / len(fk)
     write_b = 1024 * sum(wk) / len(wk)
     out = {
