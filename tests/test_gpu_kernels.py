@@ -377,7 +377,7 @@ def _splitk_case(dev, M, N, Kk, batch):
         assert (out.cpu().double() - pre * torch.sigmoid(pre)).abs().max().item() <= 2 * tol
 
 
-def test_colsum_and_layernorm_bwd_shapes(dev):
+def test_colsum_shapes_and_pitches(dev):
     for (M, N, ld) in [(23936 // 4, 256, 256), (1001, 1024, 1024), (37, 30, 33), (3, 5, 8)]:
         x = _r(M, ld, seed=16)
         out = torch.full((N,), 1.0, device=dev)
