@@ -130,6 +130,11 @@ int splitk_mode() { return g_splitk; }
 // gemm_wgrad_ws_kernel for the eligible RC x RC / RC x I2C_RC fp32 GEMMs: 0 never, 1 when its split-K grid fills the chip
 // (default), 2 whenever the launch is structurally eligible (tests: small shapes)
 int g_wgrad_ws = 1;
+// gemm_fwd_ws_kernel for the eligible KC x KC / I2C_KC x KC fp32 GEMMs on B planes (EPI_BRELU / EPI_BDR, unsplit): 0 never,
+// 1 for the shape classes that measured faster (default; the rule is in gemm_run), 2 for every eligible launch (tests:
+// small shapes)
+int g_fwd_ws = 1;
+long g_fwd_ws_launches = 0;  // launches of gemm_fwd_ws_kernel by this process (esp_get_fwd_ws_launches)
 
 // smallest K a split-K split keeps on grids of >= 64 tiles (128 before round 4's end)
 constexpr long kSplitkMinK = 256;
@@ -208,6 +213,11 @@ bool launch_glds(int MA, int MB, const GemmArgs& g, int batch, hipStream_t st, c
   x.fd_splits = make_fastdiv((uint32_t)g.splits);
   x.fd_nb2 = make_fastdiv((uint32_t)g.nb2);
   const int prec = g.bf16;
+  if (g.ws == 2) {
+    if (rs || g.splits > 1 || MB != KC || !fwd_ws_launch(MA == I2C_KC, kind, grid, st, g, x)) return false;
+    ++g_fwd_ws_launches;
+    return true;
+  }
   if (g.ws) return kind == EPI_PLAIN && wgrad_ws_launch(MB == I2C_RC, rs, grid, st, g, x);
   if (kind == EPI_PLAIN) return glds_launch_plain(MA, MB, BNT, prec, rs, grid, st, g, x);
   if (kind == EPI_FWD || kind == EPI_BWD) return glds_launch_epi(MA, MB, BNT, prec, kind, grid, st, g, x);
@@ -220,7 +230,11 @@ template <int MA, int MB>
 int launch(const GemmArgs& g0, int batch, hipStream_t st, const Operand* b_fp32 = nullptr,
            const Operand* a_fp32 = nullptr) {
   bool done = false;
-  if (g0.bnt == 64 || g0.bnt == 128) done = launch_glds(MA, MB, g0, batch, st);
+  if (g0.bnt == 64 || g0.bnt == 128 || g0.ws == 2) done = launch_glds(MA, MB, g0, batch, st);
+  if (!done && g0.ws == 2) {  // (gemm_run's eligibility rule and fwd_ws_launch disagree: no other kernel has this tile)
+    esp::set_error("esp_gemm_f32_bp: no gemm_fwd_ws_kernel for a launch the host chose it for");
+    return -1;
+  }
   GemmArgs g = g0;
   if (!done && g.bf16 == 5) {  // no planes x planes kernel for this epilogue kind: the fp32 A operand
     if (!a_fp32 || !a_fp32->p) {
@@ -309,6 +323,14 @@ ESP_API int esp_set_splitk_mode(int mode) {
   g_splitk = mode;
   return prev;
 }
+
+ESP_API int esp_set_fwd_ws(int mode) {
+  ESP_ARG_CHECK(mode >= 0 && mode <= 2, "esp_set_fwd_ws: mode must be 0, 1 or 2, got %d", mode);
+  const int prev = g_fwd_ws;
+  g_fwd_ws = mode;
+  return prev;
+}
+ESP_API long esp_get_fwd_ws_launches(void) { return g_fwd_ws_launches; }
 
 ESP_API int esp_set_wgrad_ws(int mode) {
   ESP_ARG_CHECK(mode >= 0 && mode <= 2, "esp_set_wgrad_ws: mode must be 0, 1 or 2, got %d", mode);
@@ -774,6 +796,35 @@ static int gemm_run(int mode_a, int mode_b, int M, int N, int K, int batch, int 
   }
   g.ws = ws;
   if (!ws) plan_splits(target);
+  // The long-K forward GEMMs on B planes (KC x KC with EPI_BDR / EPI_BRELU: FFN w_2; I2C_KC x KC with EPI_BRELU: the
+  // conv2 forward): gemm_fwd_ws_kernel, 128 x 256 tiles at one 512-thread block per CU, A gathered and split once
+  // per block on producer waves.  Eligible: the launch as planned above is an unsplit, unbatched PREC 3 launch with a
+  // wide epilogue of one of those kinds and no row sums, band or planes output; the gathered A under the LDS-DMA
+  // kernel's conditions (C % 32 == 0, K % 32 == 0, the 32-bit pixel offsets) plus the 24-bit pixel decode's
+  // (i2c_rc_off24_ok).  Unsplit, both kernels give the same C bit for bit, so the rule is about time alone.
+  // Auto (mode 1), for every caller the same rule on the shape: N a multiple of the 256-wide tile (no column of a
+  // tile idle), K of >= kFwsMinSlabs slabs (one block per CU exposes the tile's 128 KB store and, for EPI_BDR, its
+  // residual load: an 8-slab k-loop cannot hide them) and >= kFwsMinRounds rounds of tiles over the CUs.
+  // Measured at M = 143616, N = 256 (profiles/r25a_fwd_ws_per_shape_ab.txt): K = 256 within the rounds' spread,
+  // K = 512 1.05x, K = 1024 1.09x; at K = 1024, M = 35904 (1.1 rounds) 0.99x against M = 143616 (4.4 rounds) 1.09x.
+  // (The decoder's M ~ 15k-row w_2 is split-K today, so not eligible at all.)
+  constexpr int kFwsMinSlabs = 16, kFwsMinRounds = 4;
+  if (ESP_FWD_WS && ESP_F32_SPLIT && g_fwd_ws && !ws && g.bf16 == 3 && prec_in < 0 && mode_b == KC &&
+      (mode_a == KC || mode_a == I2C_KC) && batch == 1 && g.splits == 1 && g.bnt && !cpn && !smb && !band && !rowsum &&
+      g.wide && K >= 8 && 256L * g.b.ld * 2 < (1L << 32)) {
+    const int kind = epi_kind_spec(g);
+    bool ok = kind == EPI_BRELU || (kind == EPI_BDR && mode_a == KC);
+    if (mode_a == I2C_KC)
+      ok = ok && g.a.ic.C % GL_BK == 0 && K % GL_BK == 0 && K <= 9 * g.a.ic.C && g.a.ic.Ho > 0 && g.a.ic.Wo > 0 &&
+           2 * g.a.ic.Ho + 1 <= g.a.ic.H && 2 * g.a.ic.Wo + 1 <= g.a.ic.W && M % (g.a.ic.Ho * g.a.ic.Wo) == 0 &&
+           8L * g.a.ic.H * g.a.ic.W * g.a.ic.C < (1L << 32) && i2c_rc_off24_ok(g.a.ic, M);
+    const long rounds = ntiles(FWD_WS_BN, FWD_WS_BM) / persist_blocks(1);
+    if (ok && (g_fwd_ws == 2 || (N % FWD_WS_BN == 0 && K >= kFwsMinSlabs * GL_BK && rounds >= kFwsMinRounds))) {
+      g.bnt = FWD_WS_BN;
+      g.bm = FWD_WS_BM;
+      g.ws = 2;
+    }
+  }
   hipStream_t st = (hipStream_t)stream;
   const int key = mode_a * 4 + mode_b;
   switch (key) {

@@ -20,7 +20,8 @@
 // Global->LDS is LDS-DMA (global_load_lds_dwordx4) into a 2-slab ring: the next slab streams in while the
 // current slab's fragments are read.  The fp32 weight gradients (RC x RC: the Linears; RC x I2C_RC: conv2, B
 // gathered from the conv1 map) have a kernel of their own with the operand split on dedicated waves:
-// gemm_wgrad_ws.hip.
+// gemm_wgrad_ws.hip; so have the long-K forward GEMMs on B planes (KC x KC: FFN w_2; I2C_KC x KC: the conv2 forward,
+// A gathered from the conv1 map): gemm_fwd_ws.hip.
 // Epilogue (fused): bias, ReLU/Swish (pre-activation optionally stored to `aux`),
 // counter-RNG dropout, alpha scale and beta*R residual.
 #include <stdlib.h>
@@ -57,6 +58,13 @@ constexpr int BM = 128, BN = 128, BK = 32, NT = 256;  // BK: split-K granularity
 #define ESP_WGRAD_WS 1
 #endif
 constexpr int WGRAD_WS_BM = 256;  // its tile height (x 128 columns)
+// 1 (default): the eligible fp32 KC x KC and I2C_KC x KC GEMMs on B planes (FFN w_2 forward, conv2 forward) run
+// gemm_fwd_ws_kernel (gemm_fwd_ws.hip: A gathered and split once per block on producer waves); 0: gemm_glds_kernel
+// (an A/B build: make VARIANT=_nofws EXTRA=-DESP_FWD_WS=0)
+#ifndef ESP_FWD_WS
+#define ESP_FWD_WS 1
+#endif
+constexpr int FWD_WS_BM = 128, FWD_WS_BN = 256;  // its tile
 
 enum Mode { KC = 0, RC = 1, I2C_KC = 2, I2C_RC = 3, I2CT_KC = 4 };
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SWISH = 2, ACT_MUL = 3 /* bwd_act only: v *= pre */ };
@@ -124,6 +132,7 @@ struct GemmArgs {
   int bnt;  // LDS-DMA kernel tile width (128, or 64 for narrow / mid-size grids); 0 = fallback kernel
   int bm;   // LDS-DMA kernel tile height: 128, or 64 (with bnt 64) for under-filled grids
   int ws;   // 1: gemm_wgrad_ws_kernel (bm WGRAD_WS_BM, bnt 128; RC x RC / I2C_RC, PREC 0, plain epilogue; one block per CU)
+            // 2: gemm_fwd_ws_kernel (bm FWD_WS_BM, bnt FWD_WS_BN; KC / I2C_KC x KC, PREC 3, EPI_BRELU / EPI_BDR; one per CU)
   int bwd_act;       // != 0: backward epilogue  v = drop'(acc) * act'(pre)  (act code, dropout regenerated)
   const float* pre;  // pre-activation (same layout as C) for bwd_act
   float* rowsum;     // != NULL: rowsum[m] += sum_k A(m,k)  (bias gradient of a weight-gradient GEMM)
@@ -2534,6 +2543,9 @@ bool glds_launch_pspec(int ma, int mb, int bnt, int prec, int epi, dim3 grid, hi
 // gemm_wgrad_ws.hip: the launch of gemm_wgrad_ws_kernel (g.ws; false: not built, ESP_WGRAD_WS=0); gather_b: B is
 // an I2C_RC operand (x.c_b / hw_b / wo_b set), else RC
 bool wgrad_ws_launch(bool gather_b, bool rs, dim3 grid, hipStream_t st, const GemmArgs& g, const GldsArgs& x);
+// gemm_fwd_ws.hip: the launch of gemm_fwd_ws_kernel (g.ws == 2; false: not built, ESP_FWD_WS=0, or no such kind);
+// gather_a: A is an I2C_KC operand (x.c_a / hw_a / wo_a set), else KC; epi: EPI_BRELU or (KC only) EPI_BDR
+bool fwd_ws_launch(bool gather_a, int epi, dim3 grid, hipStream_t st, const GemmArgs& g, const GldsArgs& x);
 // an I2C_RC operand's pixel offsets fit i2c_pix_off24: Bn * H * W < 2^24 and the map < 2^32 elements (kpix: the
 // number of output pixels)
 inline bool i2c_rc_off24_ok(const Im2col& ic, long kpix) {

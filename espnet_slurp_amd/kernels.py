@@ -872,6 +872,22 @@ def set_wgrad_ws(mode: int) -> int:
     return prev
 
 
+def set_fwd_ws(mode: int) -> int:
+    """Kernel of the unsplit fp32 forward GEMMs on B planes with the bias + ReLU or bias + dropout + residual
+    epilogue -- the conv2 forward, FFN w_2 -- (esp_set_fwd_ws): 0 the LDS-DMA kernel, 1 (default) the warp-specialised
+    kernel for the shapes that measured faster, 2 wherever it is eligible.  Returns the previous mode."""
+    lib = _native.load()
+    prev = lib.esp_set_fwd_ws(int(mode))
+    if prev < 0:
+        raise _native.NativeError(f"esp_set_fwd_ws failed: {lib.esp_last_error().decode()}")
+    return prev
+
+
+def fwd_ws_launches() -> int:
+    """Launches of gemm_fwd_ws_kernel by this process so far (esp_get_fwd_ws_launches)."""
+    return int(_native.load().esp_get_fwd_ws_launches())
+
+
 def get_gemm_compute() -> int:
     return _native.load().esp_get_gemm_compute()
 

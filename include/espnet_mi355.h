@@ -83,6 +83,17 @@ int esp_set_splitk_mode(int mode);
  * == 0, Bn * H * W < 2^24 and the map holds < 2^32 elements; esp_conv2_wgrad_bf16 is not affected.  Returns the
  * previous mode. */
 int esp_set_wgrad_ws(int mode);
+/* (An addition to ABI 42.)  The kernel of the unsplit fp32 KC x KC and I2C_KC x KC GEMMs on B planes (esp_gemm_f32_bp)
+ * whose epilogue is bias + ReLU, or (KC x KC) bias + dropout + alpha + beta R -- the conv2 forward and the FFN w_2
+ * forward -- of every later launch (process-wide): 1 (default) = the warp-specialised kernel (csrc/gemm_fwd_ws.hip:
+ * 128 x 256 tiles, A gathered and split once per block on producer waves) for the shapes that measured faster
+ * (N % 256 == 0, K >= 512, >= 4 rounds of 128-row tiles over the CUs); 2 = that kernel for every structurally
+ * eligible launch (unbatched, unsplit, no row sums, wide epilogue; gathered A: C % 32 == 0, K % 32 == 0, Bn * H * W <
+ * 2^24, the map < 2^32 elements); 0 = never (the LDS-DMA kernel, as in a build with ESP_FWD_WS=0, where this call
+ * changes nothing).  Both kernels give the same C bit for bit.  Returns the previous mode. */
+int esp_set_fwd_ws(int mode);
+/* Launches of that kernel by this process so far (tests: which kernel a call took). */
+long esp_get_fwd_ws_launches(void);
 /* esp_gemm_f32 with B also given as its three bf16 split planes (esp_f32_to_planes of the fp32 B,
  * b = hi + mid + lo exactly): the same fp32 split products as esp_gemm_f32 on the fp32 B, in the same
  * order, bit for bit (split-K counts may differ: a different tile width), without splitting B in the

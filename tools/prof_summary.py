@@ -48,14 +48,16 @@ def main():
     for k, (n, t) in sorted(tot.items(), key=lambda kv: -kv[1][1]):
         print(f"{t / steps / 1e6:9.3f} {100 * t / total:6.2f} {n / steps:10.1f} {t / n / 1e3:9.1f}  {k}")
     # the bench's roofline kernel: every instantiation of the MFMA GEMM family together
-    # (gemm_wgrad_ws_kernel: the weight gradients with the operand split on producer waves)
-    fam = [(n, t) for k, (n, t) in tot.items() if "gemm_glds_kernel" in k or "gemm_wgrad_ws_kernel" in k]
+    # (gemm_wgrad_ws_kernel / gemm_fwd_ws_kernel: the weight gradients / the long-K forward GEMMs with the operand
+    # split on producer waves)
+    fams = ("gemm_glds_kernel", "gemm_wgrad_ws_kernel", "gemm_fwd_ws_kernel")
+    fam = [(n, t) for k, (n, t) in tot.items() if any(f in k for f in fams)]
     red = [(n, t) for k, (n, t) in tot.items() if "splitk_reduce" in k]
     if fam:
         n = sum(f[0] for f in fam)
         t = sum(f[1] for f in fam)
         tr = sum(f[1] for f in red)
-        print(f"# family gemm_glds_kernel<*> + gemm_wgrad_ws_kernel<*>: {n / steps:.1f} launches/step, {t / steps / 1e6:.3f} ms/step, "
+        print(f"# family {' + '.join(f + '<*>' for f in fams)}: {n / steps:.1f} launches/step, {t / steps / 1e6:.3f} ms/step, "
               f"avg {t / n / 1e3:.1f} us per launch; + split-K reductions {tr / steps / 1e6:.3f} ms/step")
     if "--gemm" in sys.argv:
         g = collections.defaultdict(lambda: [0, 0])
