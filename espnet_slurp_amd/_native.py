@@ -147,6 +147,8 @@ SIGNATURES = {
     "esp_lm_front_bwd": [P, P, P, P, P, P, F, I, F, U64, F, U64, P, P, P, P, I, I, P, L, P],
     "esp_maskctc_init": [P, I, I, I, ctypes.c_longlong, ctypes.c_double, P, P, P, P, P, P, P],
     "esp_maskctc_fill": [P, I, I, P, ctypes.c_longlong, I, P],
+    "esp_maskctc_init_batch": [P, P, I, I, I, I, ctypes.c_longlong, ctypes.c_double, I, P, P, P, P, P, P, P],
+    "esp_maskctc_fill_batch": [P, I, I, I, P, I, P, P, I, ctypes.c_longlong, I, P],
     "esp_rnnt_joint_fwd": [P, P, P, I, I, I, I, I, P],
     "esp_rnnt_joint_bwd": [P, P, P, P, P, P, I, I, I, I, I, P, L, P],
     "esp_rnnt_logprobs": [P, P, P, P, I, I, I, I, P, L, P],

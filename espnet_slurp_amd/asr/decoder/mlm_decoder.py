@@ -13,7 +13,8 @@ nor any gradient sees the difference.  forward()'s logits at padded rows therefo
 Unsupported options raise like TransformerDecoder's: the `embed` input layer (not `linear`), pre-LN, output layer.
 
 Inference (MaskCTCInference): prepare_memory (inherited) projects every layer's source-attention keys and values of
-the encoder output once; forward_masked runs the L rows of one utterance over it, once per refinement pass.
+the encoder output once; forward_masked runs the L rows of one utterance over it, once per refinement pass, and
+forward_masked_batch the rows of several ragged utterances of one prepared batch in the same launches.
 """
 from __future__ import annotations
 
@@ -78,6 +79,58 @@ class MLMDecoder(TransformerDecoder):
                 x, _ = layer.feed_forward.fwd(h, x, 1.0, 0.0, seeds, False)
             y, _ = self.after_norm.fwd(x)
             return self.output_layer.fwd(y)
+
+    def forward_masked_batch(self, y_in: torch.Tensor, ylens, mem: PreparedMemory, rows) -> torch.Tensor:
+        """forward_masked for Ua sequences in one pass: y_in (Ua, Lmax) int64 on the device (a valid id at the padded
+        positions), ylens their lengths (host, all >= 1), mem a PreparedMemory of U utterances, rows (Ua,) the
+        utterance of mem each sequence reads -> raw logits (Ua * Lmax, vocab_size + 1).  Position i of every sequence
+        gets pe[i]; self-attention is non-causal on the generic kernels with B = Ua and ylens as key counts; source
+        attention sends the Lmax rows of sequence a to utterance rows[a] with that utterance's memory length.  The
+        logits of padded rows (i >= ylens[a]) are not meant to be read; as keys those rows are masked by the key
+        count.  The key counts and the launch index are kept while (ylens, rows) repeat: every pass of a batch.  No
+        host synchronisation."""
+        self._eval_only("forward_masked_batch")
+        Ua, Lmax = (int(n) for n in y_in.shape)
+        D = self.D
+        H = self.decoders[0].self_attn.h
+        dk = D // H
+        dev = mem.kv.device
+        ylens = np.asarray(ylens, dtype=np.int32).reshape(-1)
+        rows = np.asarray(rows, dtype=np.int32).reshape(-1)
+        if ylens.shape[0] != Ua or rows.shape[0] != Ua or ylens.min() < 1 or ylens.max() > Lmax:
+            raise ValueError(f"forward_masked_batch: lengths {ylens.tolist()} / utterances {rows.tolist()} for "
+                             f"{Ua} sequences of {Lmax} positions (every length in [1, {Lmax}])")
+        with torch.no_grad():
+            pe = pos_table("abs", max(512, 1 << (Lmax - 1).bit_length()), D, dev)
+            x = torch.empty(Ua * Lmax, D, dtype=torch.float32, device=dev)
+            K.embed_fwd(y_in, self.embed[0].weight, pe, x, Lmax, math.sqrt(D), 0.0, 0)
+            klen = self._klens(ylens, dev)
+            src_idx = mem.index(np.repeat(rows, Lmax))
+            seeds = Seeds(0)
+            ctx = empty(Ua * Lmax, D, like=x)
+            for l, layer in enumerate(self.decoders):
+                ca = layer.src_attn
+                h, _ = layer.norm1.fwd(x)
+                x, _ = layer.self_attn.fwd(h, x, Ua, Lmax, klen, False, 0.0, seeds, False)
+                h, _ = layer.norm2.fwd(x)
+                q = ca.linear_q.fwd(h)
+                kv = mem.kv[l]
+                K.decode_attn(q, D, 0, kv, 2 * D, mem.T * 2 * D, 0, kv, 2 * D, mem.T * 2 * D, D, ctx, D, 0, src_idx, H,
+                              dk, mem.U, mem.T)
+                x = ca.linear_out.fwd(ctx, R=x, beta=1.0)
+                h, _ = layer.norm3.fwd(x)
+                x, _ = layer.feed_forward.fwd(h, x, 1.0, 0.0, seeds, False)
+            y, _ = self.after_norm.fwd(x)
+            return self.output_layer.fwd(y)
+
+    def _klens(self, ylens: np.ndarray, dev) -> torch.Tensor:
+        """The self-attention key counts of a batch on the device (kept while they repeat: every pass of a batch)."""
+        key = (ylens.tobytes(), str(dev))
+        c = getattr(self, "_klens_cache", None)
+        if c is None or c[0] != key:
+            c = (key, K.h2d(torch.from_numpy(np.ascontiguousarray(ylens)), dev))
+            self._klens_cache = c
+        return c[1]
 
     def _klen(self, L: int, dev) -> torch.Tensor:
         """The self-attention key count [L] on the device (kept while L repeats: every pass of an utterance)."""

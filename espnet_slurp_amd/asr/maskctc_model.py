@@ -11,6 +11,11 @@ Decoding (MaskCTCInference.forward, maskctc_model.py:284-346) runs on the device
 posteriors into the masked input, each refinement pass is one MLMDecoder.forward_masked over source-attention keys
 and values projected once, and esp_maskctc_fill takes the pass's decisions in place.  The host reads two numbers
 before the loop (L and mask_num) and the token ids after it.
+
+MaskCTCInference.forward_batch decodes U ragged utterances through the same launches: esp_maskctc_init_batch /
+esp_maskctc_fill_batch run one workgroup per utterance and keep each utterance's pass plan on the device, and
+MLMDecoder.forward_masked_batch runs a pass of all active utterances at once.  The host reads the U plans before the
+loop and the token rows after it.
 """
 from __future__ import annotations
 
@@ -140,7 +145,8 @@ class MaskCTCModel(ESPnetASRModel):
 
 
 class MaskCTCInference(nn.Module):
-    """Mask-CTC mask-predict decoding of one utterance (maskctc_model.py:262-346).
+    """Mask-CTC mask-predict decoding of one utterance (maskctc_model.py:262-346), or of a batch of them
+    (forward_batch).
 
     forward(enc_out (T, D) on the device) -> Hypothesis(yseq = [<mask>] + tokens + [<mask>]), yseq on the host.
     Reference behaviour kept as it is: a pass's argmax runs over all vocab_size + 1 classes (a position may be
@@ -170,6 +176,7 @@ class MaskCTCInference(nn.Module):
             logging.warning("MaskCTCInference: head size %d is not served by esp_decode_attn; every pass runs "
                             "MLMDecoder.run_forward and projects the memory again", dk)
         self.last = dict(L=0, mask_num=0, num_iter=0)
+        self.last_batch: List[dict] = []
 
     def ids2text(self, ids: List[int]) -> str:
         text = "".join(self.token_list[i] for i in ids)
@@ -213,3 +220,60 @@ class MaskCTCInference(nn.Module):
                     trace.append(y.clone())
         tokens = y.cpu().tolist()  # the read after the loop
         return Hypothesis(yseq=torch.tensor([self.mask_token] + tokens + [self.mask_token], dtype=torch.long))
+
+    @torch.no_grad()
+    def forward_batch(self, enc_pad: torch.Tensor, enc_lens, trace: Optional[list] = None) -> List[Hypothesis]:
+        """forward for U utterances through the same launches: enc_pad (U, Tmax, D) on the device, enc_lens (U,) on
+        the host -> one Hypothesis per utterance, what forward returns for enc_pad[u, :enc_lens[u]].
+
+        esp_maskctc_init_batch masks every utterance and leaves each one's pass plan {L, mask_num, num_iter, k} on
+        the device; the host reads all plans once.  The utterances with a pass to run (the active set) go through
+        MLMDecoder.forward_masked_batch as one batch of the longest active L, once per pass for the largest num_iter;
+        esp_maskctc_fill_batch applies pass t by each utterance's own plan, so an utterance whose passes are done
+        idles in the batch untouched.  Utterances with L == 0 or mask_num == 0 never reach the decoder.  No host read
+        inside the loop, one read of the token rows after it.
+
+        trace: receives the (U, Tmax) device token array after the masking and after every pass (clones; row u is
+        valid up to L_u).  `last_batch` keeps every utterance's {L, mask_num, num_iter}."""
+        if self.mlm.training or self.ctc.training:
+            raise RuntimeError("MaskCTCInference.forward_batch: inference only (call .eval() on the model)")
+        if enc_pad.dim() != 3:
+            raise ValueError(f"forward_batch: enc_pad of shape {tuple(enc_pad.shape)}, expected (U, Tmax, D)")
+        U, Tmax, dev = int(enc_pad.shape[0]), int(enc_pad.shape[1]), enc_pad.device
+        lens = numpy.asarray(torch.as_tensor(enc_lens).cpu(), dtype=numpy.int32).reshape(-1)
+        if U < 1 or lens.shape[0] != U or lens.min() < 1 or lens.max() > Tmax:
+            raise ValueError(f"forward_batch: enc_lens {lens.tolist()} for enc_pad of shape {tuple(enc_pad.shape)}")
+        enc_pad = enc_pad.to(torch.float32).contiguous()
+        lp = self.ctc.log_softmax(enc_pad)
+        tlens = K.h2d(torch.from_numpy(lens), dev)
+        y_all, _, _, counts = K.maskctc_init_batch(lp, tlens, self.mask_token, self.threshold_probability,
+                                                   self.n_iterations, self.blank_id)
+        plan = counts.cpu().numpy()  # the one read before the loop
+        self.last_batch = [dict(L=int(r[0]), mask_num=int(r[1]), num_iter=int(r[2])) for r in plan]
+        if trace is not None:
+            trace.append(y_all.clone())
+        active = numpy.nonzero(plan[:, 2] > 0)[0].astype(numpy.int32)
+        if active.size:
+            Lmax, passes = int(plan[active, 0].max()), int(plan[active, 2].max())
+            ylens = plan[active, 0].astype(numpy.int32)
+            rows32 = K.h2d(torch.from_numpy(active), dev)
+            rows64 = rows32.to(torch.int64)
+            y_view = y_all[:, :Lmax]
+            if self.prepared_memory:
+                mem = self.mlm.prepare_memory(enc_pad, lens)
+            else:
+                hs, hl = enc_pad.index_select(0, rows64), K.h2d(torch.from_numpy(lens[active]), dev)
+                yl = K.h2d(torch.from_numpy(ylens), dev)
+            for t in range(passes):
+                y = y_view.index_select(0, rows64)  # (Ua, Lmax), contiguous
+                if self.prepared_memory:
+                    logits = self.mlm.forward_masked_batch(y, ylens, mem, active)
+                else:
+                    logits, _ = self.mlm.run_forward(hs, hl, y, yl, Seeds(0), False)
+                K.maskctc_fill_batch(logits.view(active.size, Lmax, -1), y_all, counts, rows32, self.mask_token, t)
+                if trace is not None:
+                    trace.append(y_all.clone())
+        tokens = y_all.cpu().numpy()  # the read after the loop
+        m = self.mask_token
+        return [Hypothesis(yseq=torch.tensor([m] + tokens[u, :int(plan[u, 0])].tolist() + [m], dtype=torch.long))
+                for u in range(U)]

@@ -1,6 +1,8 @@
 // Mask-CTC mask-predict decoding on the device (espnet2/asr/maskctc_model.py MaskCTCInference.forward):
 //   esp_maskctc_init  greedy CTC -> collapsed tokens, their confidences, the masked decoder input (:288-317)
 //   esp_maskctc_fill  one refinement step on the decoder's logits (:327-331, :336-337)
+//   esp_maskctc_init_batch / esp_maskctc_fill_batch  the same device bodies for U ragged utterances, grid = U, with
+//                     the per-utterance pass plan (num_iter, k: :319-323) kept on the device
 // One workgroup per utterance, 4 waves; selection only (max / argmax / rank), so every id and every selected
 // value is reproducible bit for bit.  Plain C++ and vector stores, wave64 shuffles, no atomics.
 #include "common.h"
@@ -50,12 +52,13 @@ __device__ __forceinline__ int block_excl_scan(int v, int* sh /* >= MC_NT / 64 *
   return base + incl - v;
 }
 
-__global__ __launch_bounds__(MC_NT) void maskctc_init_kernel(const float* __restrict__ lp, int T, int V, int blank,
-                                                            long long mask_token, double thr, int* __restrict__ fid,
-                                                            float* __restrict__ flp, long long* __restrict__ y_in,
-                                                            float* __restrict__ tok_logp, float* __restrict__ tok_prob,
-                                                            int* __restrict__ counts) {
-  __shared__ int sh[MC_NT / 64];
+// esp_maskctc_init's work for one utterance, by the whole block: returns L, nmask_total the masked tokens (both
+// block-uniform)
+__device__ __forceinline__ int maskctc_init_body(const float* __restrict__ lp, int T, int V, int blank,
+                                                 long long mask_token, double thr, int* __restrict__ fid,
+                                                 float* __restrict__ flp, long long* __restrict__ y_in,
+                                                 float* __restrict__ tok_logp, float* __restrict__ tok_prob, int* sh,
+                                                 int& nmask_total) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // 1. per-frame argmax of the log-probabilities (exp is monotone: the argmax of the probabilities)
   for (int t = w; t < T; t += MC_NT / 64) {
@@ -92,18 +95,50 @@ __global__ __launch_bounds__(MC_NT) void maskctc_init_kernel(const float* __rest
     }
     base += total;
   }
-  int total;
-  block_excl_scan(nmask, sh, total);
+  block_excl_scan(nmask, sh, nmask_total);
+  return base;
+}
+
+__global__ __launch_bounds__(MC_NT) void maskctc_init_kernel(const float* __restrict__ lp, int T, int V, int blank,
+                                                            long long mask_token, double thr, int* __restrict__ fid,
+                                                            float* __restrict__ flp, long long* __restrict__ y_in,
+                                                            float* __restrict__ tok_logp, float* __restrict__ tok_prob,
+                                                            int* __restrict__ counts) {
+  __shared__ int sh[MC_NT / 64];
+  int nmask;
+  const int L = maskctc_init_body(lp, T, V, blank, mask_token, thr, fid, flp, y_in, tok_logp, tok_prob, sh, nmask);
   if (threadIdx.x == 0) {
-    counts[0] = base;
-    counts[1] = total;
+    counts[0] = L;
+    counts[1] = nmask;
   }
 }
 
-__global__ __launch_bounds__(MC_NT) void maskctc_fill_kernel(const float* __restrict__ logits, int L, int V1,
-                                                            long long* __restrict__ y_in, long long mask_token, int k) {
-  __shared__ float score[MC_FILL_MAXL];
-  __shared__ int arg[MC_FILL_MAXL];  // -1: the position is not masked
+// one workgroup per utterance: frames [0, tlens[u]) of its (Tmax, V) block, the pass plan into counts[u]
+__global__ __launch_bounds__(MC_NT) void maskctc_init_batch_kernel(
+    const float* __restrict__ lp, const int* __restrict__ tlens, int Tmax, int V, int blank, long long mask_token,
+    double thr, int n_iterations, int* __restrict__ fid, float* __restrict__ flp, long long* __restrict__ y_in,
+    float* __restrict__ tok_logp, float* __restrict__ tok_prob, int* __restrict__ counts) {
+  __shared__ int sh[MC_NT / 64];
+  const int u = blockIdx.x;
+  const long o = (long)u * Tmax;
+  const int T = min(max(tlens[u], 0), Tmax);
+  int nmask;
+  const int L = maskctc_init_body(lp + o * V, T, V, blank, mask_token, thr, fid + o, flp + o, y_in + o, tok_logp + o,
+                                  tok_prob + o, sh, nmask);
+  for (int i = L + threadIdx.x; i < Tmax; i += MC_NT) y_in[o + i] = 0;
+  if (threadIdx.x == 0) {
+    const int num_iter = (nmask >= n_iterations && n_iterations > 0) ? n_iterations : nmask;
+    counts[4 * u + 0] = L;
+    counts[4 * u + 1] = nmask;
+    counts[4 * u + 2] = num_iter;
+    counts[4 * u + 3] = num_iter > 0 ? nmask / num_iter : 0;
+  }
+}
+
+// esp_maskctc_fill's work for one utterance, by the whole block; score / arg: MC_FILL_MAXL entries of LDS each
+__device__ __forceinline__ void maskctc_fill_body(const float* __restrict__ logits, int L, int V1,
+                                                  long long* __restrict__ y_in, long long mask_token, int k,
+                                                  float* score, int* arg /* -1: the position is not masked */) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int i = w; i < L; i += MC_NT / 64) {
     const bool masked = y_in[i] == mask_token;  // wave-uniform
@@ -129,6 +164,31 @@ __global__ __launch_bounds__(MC_NT) void maskctc_fill_kernel(const float* __rest
   }
 }
 
+__global__ __launch_bounds__(MC_NT) void maskctc_fill_kernel(const float* __restrict__ logits, int L, int V1,
+                                                            long long* __restrict__ y_in, long long mask_token, int k) {
+  __shared__ float score[MC_FILL_MAXL];
+  __shared__ int arg[MC_FILL_MAXL];
+  maskctc_fill_body(logits, L, V1, y_in, mask_token, k, score, arg);
+}
+
+// workgroup a: pass t of utterance rows[a] on logits block a, by that utterance's plan counts[u] = {L, mask_num,
+// num_iter, k}.  The skip follows the plan, not the masks: a position filled with <mask> by the last pass stays.
+__global__ __launch_bounds__(MC_NT) void maskctc_fill_batch_kernel(const float* __restrict__ logits, int Lmax, int V1,
+                                                                  long long* __restrict__ y_in, int ld,
+                                                                  const int* __restrict__ counts,
+                                                                  const int* __restrict__ rows, int U,
+                                                                  long long mask_token, int t) {
+  __shared__ float score[MC_FILL_MAXL];
+  __shared__ int arg[MC_FILL_MAXL];
+  const int a = blockIdx.x, u = rows[a];
+  if (u < 0 || u >= U) return;  // block-uniform, as every return below
+  const int L = min(max(counts[4 * u], 0), Lmax), num_iter = counts[4 * u + 2];
+  if (t >= num_iter) return;
+  const int k = t < num_iter - 1 ? counts[4 * u + 3] : 0;
+  if (t < num_iter - 1 && k <= 0) return;  // not a plan esp_maskctc_init_batch writes (k >= 1 there)
+  maskctc_fill_body(logits + (long)a * Lmax * V1, L, V1, y_in + (long)u * ld, mask_token, k, score, arg);
+}
+
 }  // namespace
 
 ESP_API int esp_maskctc_init(const float* lp, int T, int V, int blank, long long mask_token, double threshold, int* fid,
@@ -148,5 +208,29 @@ ESP_API int esp_maskctc_fill(const float* logits, int L, int V1, long long* y_in
   hipLaunchKernelGGL(maskctc_fill_kernel, dim3(1), dim3(MC_NT), 0, (hipStream_t)stream, logits, L, V1, y_in, mask_token,
                      k);
   ESP_CHECK_LAUNCH("esp_maskctc_fill");
+  return 0;
+}
+
+ESP_API int esp_maskctc_init_batch(const float* lp, const int* tlens, int U, int Tmax, int V, int blank,
+                                   long long mask_token, double threshold, int n_iterations, int* fid, float* flp,
+                                   long long* y_in, float* tok_logp, float* tok_prob, int* counts, void* stream) {
+  ESP_ARG_CHECK(U >= 1 && Tmax >= 1 && V >= 1 && blank >= 0 && blank < V && n_iterations >= 0,
+                "esp_maskctc_init_batch: bad sizes U=%d Tmax=%d V=%d blank=%d n_iterations=%d", U, Tmax, V, blank,
+                n_iterations);
+  hipLaunchKernelGGL(maskctc_init_batch_kernel, dim3(U), dim3(MC_NT), 0, (hipStream_t)stream, lp, tlens, Tmax, V, blank,
+                     mask_token, threshold, n_iterations, fid, flp, y_in, tok_logp, tok_prob, counts);
+  ESP_CHECK_LAUNCH("esp_maskctc_init_batch");
+  return 0;
+}
+
+ESP_API int esp_maskctc_fill_batch(const float* logits, int Ua, int Lmax, int V1, long long* y_in, int ld,
+                                   const int* counts, const int* rows, int U, long long mask_token, int t,
+                                   void* stream) {
+  ESP_ARG_CHECK(Ua >= 1 && U >= 1 && Lmax >= 1 && Lmax <= MC_FILL_MAXL && V1 >= 1 && ld >= Lmax && t >= 0,
+                "esp_maskctc_fill_batch: bad sizes Ua=%d U=%d Lmax=%d (max %d) V1=%d ld=%d t=%d", Ua, U, Lmax,
+                MC_FILL_MAXL, V1, ld, t);
+  hipLaunchKernelGGL(maskctc_fill_batch_kernel, dim3(Ua), dim3(MC_NT), 0, (hipStream_t)stream, logits, Lmax, V1, y_in,
+                     ld, counts, rows, U, mask_token, t);
+  ESP_CHECK_LAUNCH("esp_maskctc_fill_batch");
   return 0;
 }

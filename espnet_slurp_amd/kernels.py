@@ -1702,6 +1702,45 @@ def maskctc_fill(logits, y_in, mask_token, k):
     _native.call("esp_maskctc_fill", _p(logits), L, V1, _p(y_in), int(mask_token), int(k), _st())
 
 
+def maskctc_init_batch(lp, tlens_i32, mask_token, threshold, n_iterations, blank=0):
+    """maskctc_init for U ragged utterances in one launch (esp_maskctc_init_batch): lp (U, Tmax, V) fp32
+    log-softmax, tlens_i32 (U,) device int32; utterance u reads frames [0, tlens[u]) only.  Returns (y_in (U, Tmax)
+    int64, tok_logp, tok_prob (U, Tmax), counts (U, 4) int32 = {L, mask_num, num_iter, k}: the reference's pass plan
+    under n_iterations), all on the device; row u's first L_u entries are valid, y_in is 0 beyond them.  No host
+    synchronisation."""
+    U, Tmax, V = lp.shape
+    _f32(lp)
+    assert lp.is_contiguous() and tlens_i32.dtype == torch.int32 and tlens_i32.shape == (U,)
+    assert tlens_i32.is_contiguous() and tlens_i32.device == lp.device
+    dev = lp.device
+    fid = torch.empty(U, Tmax, dtype=torch.int32, device=dev)
+    flp = torch.empty(U, Tmax, dtype=torch.float32, device=dev)
+    y_in = torch.empty(U, Tmax, dtype=torch.int64, device=dev)
+    tok_logp = torch.empty(U, Tmax, dtype=torch.float32, device=dev)
+    tok_prob = torch.empty(U, Tmax, dtype=torch.float32, device=dev)
+    counts = torch.empty(U, 4, dtype=torch.int32, device=dev)
+    _native.call("esp_maskctc_init_batch", _p(lp), _p(tlens_i32), U, Tmax, V, int(blank), int(mask_token),
+                 float(threshold), int(n_iterations), _p(fid), _p(flp), _p(y_in), _p(tok_logp), _p(tok_prob),
+                 _p(counts), _st())
+    return y_in, tok_logp, tok_prob, counts
+
+
+def maskctc_fill_batch(logits, y_in, counts, rows_i32, mask_token, t):
+    """Pass t of the mask-predict loop in place for the utterances rows_i32 (esp_maskctc_fill_batch): logits (Ua,
+    Lmax, V + 1) fp32 raw decoder outputs, block a belonging to utterance rows_i32[a] (Ua device int32, distinct);
+    y_in (U, >= Lmax) int64 and counts (U, 4) int32 as maskctc_init_batch returns them.  An utterance whose plan has
+    fewer than t + 1 passes is left alone.  No host synchronisation."""
+    Ua, Lmax, V1 = logits.shape
+    _f32(logits)
+    assert logits.is_contiguous() and y_in.dtype == torch.int64 and y_in.dim() == 2 and y_in.stride(1) == 1
+    U, ld = y_in.shape[0], (y_in.stride(0) if y_in.shape[0] > 1 else y_in.shape[1])
+    assert counts.dtype == torch.int32 and counts.shape == (U, 4) and counts.is_contiguous()
+    assert rows_i32.dtype == torch.int32 and rows_i32.shape == (Ua,) and rows_i32.is_contiguous()
+    assert y_in.device == logits.device == counts.device == rows_i32.device
+    _native.call("esp_maskctc_fill_batch", _p(logits), Ua, Lmax, V1, _p(y_in), int(ld), _p(counts), _p(rows_i32), U,
+                 int(mask_token), int(t), _st())
+
+
 # ----------------------------------------------------------------------------- Transformer LM step
 LM_STEP_FUSED = True   # the LM step's linears on esp_step_linear (5 launches per layer); False: generic kernels
 LM_STEP_MAX_ROWS = 512  # rows up to which the fused step is used (measured: DESIGN 3.6b); above: the generic kernels

@@ -685,6 +685,26 @@ int esp_maskctc_init(const float* lp, int T, int V, int blank, long long mask_to
                      float* flp, long long* y_in, float* tok_logp, float* tok_prob, int* counts, void* stream);
 int esp_maskctc_fill(const float* logits, int L, int V1, long long* y_in, long long mask_token, int k, void* stream);
 
+/* The same two steps for U ragged utterances, one workgroup per utterance (grid = U), on the device bodies of the
+ * entry points above: a U = 1 batch writes what they write, bit for bit.  No atomics, no workgroup waits for another.
+ *
+ * esp_maskctc_init_batch: lp (U, Tmax, V) fp32; tlens (U) device int32 (clamped to [0, Tmax]).  Utterance u reads
+ * frames [0, tlens[u]) only.  y_in / tok_logp / tok_prob / fid / flp: (U, Tmax); row u's first L_u entries are
+ * esp_maskctc_init's for that utterance alone, y_in[u, i >= L_u] = 0.  counts (U, 4) int32 = {L, mask_num, num_iter,
+ * k}, the reference's pass plan (:319-323): num_iter = n_iterations if mask_num >= n_iterations > 0 else mask_num;
+ * k = mask_num / num_iter (0 when num_iter == 0).
+ *
+ * esp_maskctc_fill_batch: pass t on logits (Ua, Lmax, V1) fp32; workgroup a serves utterance u = rows[a] (Ua device
+ * int32, distinct, in [0, U); others are skipped): row u of y_in (U, ld) int64 in place, positions [0, L_u).
+ * t >= num_iter_u: untouched (by the plan, not by "no masks left": a position whose argmax was <mask> in the last
+ * pass stays); t < num_iter_u - 1: esp_maskctc_fill with k_u; t == num_iter_u - 1: with k = 0.
+ * 1 <= Lmax <= 2048, ld >= Lmax (else status -1). */
+int esp_maskctc_init_batch(const float* lp, const int* tlens, int U, int Tmax, int V, int blank, long long mask_token,
+                           double threshold, int n_iterations, int* fid, float* flp, long long* y_in, float* tok_logp,
+                           float* tok_prob, int* counts, void* stream);
+int esp_maskctc_fill_batch(const float* logits, int Ua, int Lmax, int V1, long long* y_in, int ld, const int* counts,
+                           const int* rows, int U, long long mask_token, int t, void* stream);
+
 /* ---- ABI 42: Transformer LM training (espnet2/lm/transformer_lm.py forward, espnet2/lm/espnet_model.py).
  *
  * esp_causal_attn_fwd / _bwd (csrc/causal_attn.hip): causal self-attention of B sequences of L tokens, one workgroup
