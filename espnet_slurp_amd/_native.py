@@ -47,6 +47,8 @@ SIGNATURES = {
     "esp_set_wgrad_ws": [I],
     "esp_set_fwd_ws": [I],
     "esp_get_fwd_ws_launches": [],
+    "esp_set_dgrad_ws": [I],
+    "esp_get_dgrad_ws_launches": [],
     "esp_act_bwd": [P, P, P, L, I, F, U64, L, P],
     "esp_scale_dropout": [P, P, L, F, F, U64, P, F, P],
     "esp_scale_dropout_planes": [P, P, L, L, I, F, F, U64, P],
@@ -173,6 +175,7 @@ SIGNATURES = {
 }
 _RESTYPES = {"esp_last_error": ctypes.c_char_p, "esp_abi_version": I, "esp_attn_slot_check_errors": I, "esp_set_gemm_compute": I,
              "esp_get_gemm_compute": I, "esp_set_splitk_mode": I, "esp_set_wgrad_ws": I, "esp_set_fwd_ws": I, "esp_get_fwd_ws_launches": L,
+             "esp_set_dgrad_ws": I, "esp_get_dgrad_ws_launches": L,
              "esp_f32_gemm_products": I}
 _RESTYPES.update({k: L for k in SIGNATURES if k.endswith("_workspace_bytes")})
 ABI_VERSION = 42  # bumped whenever a signature in include/espnet_mi355.h changes

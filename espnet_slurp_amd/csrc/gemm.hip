@@ -120,7 +120,6 @@ long persist_blocks(int per_cu) {
 }
 
 int g_compute = 0;  // 0: fp32 MFMA (exact f32 fma chain), 1: bf16-input MFMA with fp32 accumulate
-int g_last_grid = 0;  // the grid of the last LDS-DMA launch (EPI_C1FOLD: its per-block records)
 
 // split-K combine: 0 the reduction launch (default), 1 in-kernel (last-arriving unit per tile;
 // measured slower, kept for esp_set_splitk_mode and its parity test)
@@ -135,6 +134,10 @@ int g_wgrad_ws = 1;
 // small shapes)
 int g_fwd_ws = 1;
 long g_fwd_ws_launches = 0;  // launches of gemm_fwd_ws_kernel by this process (esp_get_fwd_ws_launches)
+// gemm_dgrad_ws_kernel for the eligible conv2 input-gradient class GEMMs (I2CT_KC x RC on B planes): 0 never, 1 for the
+// classes that measured faster (default; the rule is in conv2_dgrad_impl), 2 for every eligible launch (tests)
+int g_dgrad_ws = 1;
+long g_dgrad_ws_launches = 0;  // launches of gemm_dgrad_ws_kernel by this process (esp_get_dgrad_ws_launches)
 
 // smallest K a split-K split keeps on grids of >= 64 tiles (128 before round 4's end)
 constexpr long kSplitkMinK = 256;
@@ -153,8 +156,10 @@ constexpr long kMaxSplits = 128;
 // Launch the LDS-DMA kernel with the epilogue kind compiled in (each kind is its own kernel,
 // so the plain GEMMs carry none of the fused epilogues' registers; the instantiations live in
 // the gemm_glds_*.hip units).  Returns false when the mode pair has no instantiation of the
-// needed kind (the caller falls back to the register-staged kernel).
-bool launch_glds(int MA, int MB, const GemmArgs& g, int batch, hipStream_t st, const GldsArgs* tconv = nullptr) {
+// needed kind (the caller falls back to the register-staged kernel).  grid_out: the grid of the launch (EPI_C1FOLD:
+// the number of per-block records it writes).
+bool launch_glds(int MA, int MB, const GemmArgs& g, int batch, hipStream_t st, const GldsArgs* tconv = nullptr,
+                 int* grid_out = nullptr) {
   const int BNT = g.bnt;
   const bool can_rs = MA == RC;
   const bool can_fwd = (MA == KC && (MB == KC || MB == RC)) || (MA == I2C_KC && MB == KC);
@@ -204,15 +209,22 @@ bool launch_glds(int MA, int MB, const GemmArgs& g, int batch, hipStream_t st, c
   x.ntiles = (int)((long)x.ntx * x.nty * batch * g.splits);
   const bool rs = can_rs && g.rowsum;
   if (rs) kind = EPI_PLAIN;
-  if (kind == EPI_C1FOLD && !(MA == I2CT_KC && MB == RC && BNT == 128 && bm == 128 && x.ntx <= C1NT)) return false;
+  if (kind == EPI_C1FOLD && g.ws != 3 && !(MA == I2CT_KC && MB == RC && BNT == 128 && bm == 128 && x.ntx <= C1NT))
+    return false;
   const dim3 grid((unsigned)std::min<long>(x.ntiles, persist_blocks(g.ws ? 1 : glds_occupancy_rt(BNT, kind, bm, g.bf16))));
-  g_last_grid = (int)grid.x;
+  if (grid_out) *grid_out = (int)grid.x;
   x.fd_grid = make_fastdiv(grid.x);
   x.fd_ntx = make_fastdiv((uint32_t)x.ntx);
   x.fd_nty = make_fastdiv((uint32_t)x.nty);
   x.fd_splits = make_fastdiv((uint32_t)g.splits);
   x.fd_nb2 = make_fastdiv((uint32_t)g.nb2);
   const int prec = g.bf16;
+  if (g.ws == 3) {  // (conv2_dgrad_impl's eligibility rule)
+    if (rs || g.splits > 1 || batch != 1 || MA != I2CT_KC || MB != RC || prec != 3 || !dgrad_ws_launch(kind, grid, st, g, x))
+      return false;
+    ++g_dgrad_ws_launches;
+    return true;
+  }
   if (g.ws == 2) {
     if (rs || g.splits > 1 || MB != KC || !fwd_ws_launch(MA == I2C_KC, kind, grid, st, g, x)) return false;
     ++g_fwd_ws_launches;
@@ -331,6 +343,14 @@ ESP_API int esp_set_fwd_ws(int mode) {
   return prev;
 }
 ESP_API long esp_get_fwd_ws_launches(void) { return g_fwd_ws_launches; }
+
+ESP_API int esp_set_dgrad_ws(int mode) {
+  ESP_ARG_CHECK(mode >= 0 && mode <= 2, "esp_set_dgrad_ws: mode must be 0, 1 or 2, got %d", mode);
+  const int prev = g_dgrad_ws;
+  g_dgrad_ws = mode;
+  return prev;
+}
+ESP_API long esp_get_dgrad_ws_launches(void) { return g_dgrad_ws_launches; }
 
 ESP_API int esp_set_wgrad_ws(int mode) {
   ESP_ARG_CHECK(mode >= 0 && mode <= 2, "esp_set_wgrad_ws: mode must be 0, 1 or 2, got %d", mode);
@@ -1029,6 +1049,7 @@ static int conv2_dgrad_impl(const float* dz2, const void* dz2_16, const float* W
     t.t_hw = make_fastdiv((uint32_t)(Ha * We));
     t.t_w = make_fastdiv((uint32_t)We);
     t.t_T2 = T2; t.t_F2 = F2; t.t_C = b16 ? D / 2 : D;  // (bf16: channel pairs)
+    t.c_a = make_fastdiv((uint32_t)t.t_C);  // (gemm_dgrad_ws_kernel's tap of a slab)
     for (int ti = 0; ti < ntap; ++ti) {
       const int kt = ph ? 1 : 2 * (ti / nkf), kf = pw ? 1 : 2 * (ti % nkf);
       t.t_dt[ti] = (kt - ph) / 2;
@@ -1064,15 +1085,34 @@ static int conv2_dgrad_impl(const float* dz2, const void* dz2_16, const float* W
     g.cmap = 1;
     g.cm_hw = t.t_hw; g.cm_w = t.t_w;
     g.cm_T1 = T1; g.cm_F1 = F1; g.cm_ph = ph; g.cm_pw = pw;
-    if (!launch_glds(I2CT_KC, RC, g, 1, st, &t)) {
+    // gemm_dgrad_ws_kernel (128 x 256 tiles at one 512-thread block per CU, dz2 gathered and split once per block on
+    // producer waves).  Eligible: the PREC 3 path with the mask as a bit map (EPI_RMASKMAP / EPI_C1FOLD), D a multiple
+    // of its 256-wide tile within the fold's records (D <= 512), and the row / source-pixel decode's limits: class
+    // rows and dz2 pixels < 2^24 (24-bit multiplies), dz2 < 2^32 elements.  Both kernels give the same masked dz1
+    // bit for bit (the fold: the same per-tile sums in another order over blocks), so the rule is about time alone.
+    // Auto (mode 1): >= kDgwsMinRounds rounds of 128-row tiles over the CUs, and the class's K among those that
+    // measured faster in every A/B round (kDgwsAutoTaps, bit ntap - 1; profiles/r30a_dgrad_ws_per_shape_ab.txt).
+    constexpr long kDgwsMinRounds = 4;
+    constexpr unsigned kDgwsAutoTaps = 0xB;  // K = 4D, 2D, D
+    if (ESP_DGRAD_WS && g_dgrad_ws && bp && z1bits && D % FWD_WS_BN == 0 && D <= 128 * C1NT && g.M < (1L << 24) &&
+        (long)B * T2 * F2 < (1L << 24) && (long)B * T2 * F2 * D < (1L << 32)) {
+      const long rounds = ((g.M + FWD_WS_BM - 1) / FWD_WS_BM) * (D / FWD_WS_BN) / persist_blocks(1);
+      if (g_dgrad_ws == 2 || (rounds >= kDgwsMinRounds && ((kDgwsAutoTaps >> (ntap - 1)) & 1u))) {
+        g.bnt = FWD_WS_BN;
+        g.bm = FWD_WS_BM;
+        g.ws = 3;
+      }
+    }
+    int grid = 0;
+    if (!launch_glds(I2CT_KC, RC, g, 1, st, &t, &grid)) {
       esp::set_error("esp_conv2_dgrad: no kernel for the class GEMM");
       return -1;
     }
     ESP_CHECK_LAUNCH("esp_conv2_dgrad");
     if (c1) {
       c1r.off[cls] = c1off;
-      c1r.grid[cls] = g_last_grid;
-      c1off += (long)g_last_grid * C1NT * 256 * 10;
+      c1r.grid[cls] = grid;
+      c1off += (long)grid * C1NT * 256 * 10;
     }
   }
   if (c1) {

@@ -42,50 +42,10 @@ namespace espg {
 namespace {
 
 constexpr int FW_NT = 512;
-constexpr int FW_PLA = FWD_WS_BM * 64, FW_PLB = FWD_WS_BN * 64;  // bytes of one A / B plane image
+constexpr int FW_PLB = FWD_WS_BN * 64;                           // bytes of one B plane image (A: FW_PLA)
 constexpr int FW_STB = 3 * (FW_PLA + FW_PLB);                    // bytes of one stage
 
-// a producer lane's share of an A slab (128 rows x 32 k): 8 lanes cover a row's 32 k (128 bytes), a wave 8 rows per
-// load, the four waves 32; load i takes rows 32 i + rl.  pl_kc_swz(rl + 32 i) == pl_kc_swz(rl), so the lane's byte
-// offset in a plane image advances by 32 rows per load.
-template <bool GA>
-struct FwStageA {
-  static constexpr int NI = FWD_WS_BM / 32;
-  int rl, kq;    // tile row of load 0; k offset of the lane's quad inside a slab
-  uint32_t lds;  // byte offset of the lane's 8 bytes of row rl in a plane image
-  __device__ __forceinline__ void init_lane(int pw, int lane) {
-    const int qd = lane & 7;
-    rl = 8 * pw + (lane >> 3);
-    kq = 4 * qd;
-    lds = (uint32_t)(rl * 64 + (((qd >> 1) ^ pl_kc_swz(rl)) << 4) + 8 * (qd & 1));
-  }
-  // the slab's tap and channel offset (GA; k0 % 32 == 0 and C % 32 == 0: a slab lies inside one tap)
-  __device__ __forceinline__ long tap_off(const GemmArgs& g, const GldsArgs& x, int k0) const {
-    const int t = (int)fdiv((uint32_t)k0, x.c_a), kt = t / 3, kf = t - 3 * kt;
-    return ((long)kt * g.a.ic.W + kf) * g.a.ic.C + (k0 - t * g.a.ic.C);
-  }
-  // load i of the slab at k0 of the tile at row m0 (rows past M read the last row; KC: quads past K the last quad)
-  __device__ __forceinline__ float4 load(const GemmArgs& g, const GldsArgs& x, int m0, int k0, long tap, int i) const {
-    const int m = min(m0 + rl + 32 * i, g.M - 1);
-    if constexpr (GA) {
-      const float* p = g.a.p + tap + kq;
-      return *reinterpret_cast<const float4*>(p + i2c_pix_off24(g.a.ic, x.hw_a, x.wo_a, (uint32_t)m));
-    } else {
-      return *reinterpret_cast<const float4*>(g.a.p + (long)m * g.a.ld + min(k0 + kq, g.K - 4));
-    }
-  }
-  // split load i's quad and write the planes; quads at k >= kv are written as zeros
-  __device__ __forceinline__ void store(float4 w, int i, char* planes, int kv) const {
-    if (!GA && kq >= kv) w = make_float4(0.f, 0.f, 0.f, 0.f);
-    uint32_t h0, m0, l0, h1, m1, l1;
-    esp::split3_pair<false>(w.x, w.y, h0, m0, l0);
-    esp::split3_pair<false>(w.z, w.w, h1, m1, l1);
-    char* d = planes + lds + i * 32 * 64;
-    *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
-    *reinterpret_cast<uint2*>(d + FW_PLA) = make_uint2(m0, m1);
-    *reinterpret_cast<uint2*>(d + 2 * FW_PLA) = make_uint2(l0, l1);
-  }
-};
+// (a producer lane's share of an A slab: FwStageA, gemm_kernels.h)
 
 // GA: A gathered from an NHWC map (I2C_KC) instead of read as a row-major [M][K] matrix (KC)
 template <bool GA, int EPI>

@@ -65,6 +65,12 @@ constexpr int WGRAD_WS_BM = 256;  // its tile height (x 128 columns)
 #define ESP_FWD_WS 1
 #endif
 constexpr int FWD_WS_BM = 128, FWD_WS_BN = 256;  // its tile
+// 1 (default): the eligible fp32 I2CT_KC x RC GEMMs on B planes (the conv2 input gradient's parity classes) run
+// gemm_dgrad_ws_kernel (gemm_dgrad_ws.hip: dz2 gathered and split once per block on producer waves, the same tile);
+// 0: gemm_glds_kernel (an A/B build: make VARIANT=_nodws EXTRA=-DESP_DGRAD_WS=0)
+#ifndef ESP_DGRAD_WS
+#define ESP_DGRAD_WS 1
+#endif
 
 enum Mode { KC = 0, RC = 1, I2C_KC = 2, I2C_RC = 3, I2CT_KC = 4 };
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SWISH = 2, ACT_MUL = 3 /* bwd_act only: v *= pre */ };
@@ -133,6 +139,7 @@ struct GemmArgs {
   int bm;   // LDS-DMA kernel tile height: 128, or 64 (with bnt 64) for under-filled grids
   int ws;   // 1: gemm_wgrad_ws_kernel (bm WGRAD_WS_BM, bnt 128; RC x RC / I2C_RC, PREC 0, plain epilogue; one block per CU)
             // 2: gemm_fwd_ws_kernel (bm FWD_WS_BM, bnt FWD_WS_BN; KC / I2C_KC x KC, PREC 3, EPI_BRELU / EPI_BDR; one per CU)
+            // 3: gemm_dgrad_ws_kernel (the same tile; I2CT_KC x RC, PREC 3, EPI_RMASKMAP / EPI_C1FOLD; one per CU)
   int bwd_act;       // != 0: backward epilogue  v = drop'(acc) * act'(pre)  (act code, dropout regenerated)
   const float* pre;  // pre-activation (same layout as C) for bwd_act
   float* rowsum;     // != NULL: rowsum[m] += sum_k A(m,k)  (bias gradient of a weight-gradient GEMM)
@@ -156,7 +163,8 @@ struct GemmArgs {
   int cm_bw;
   // EPI_C1FOLD: the masked input gradient of the conv1 map is not stored; its conv1 weight / bias gradient
   // partials (x = the conv1 input, T x F per utterance) accumulate per wave in registers across the block's
-  // tiles and land in c1_part, [grid][tn C1NT][wave 4][lane 64][10] (c1fold_reduce / c1fold_finalize)
+  // tiles and land in c1_part, [grid][tn C1NT][wave 4][lane 64][10] (c1fold_reduce / c1fold_finalize;
+  // gemm_dgrad_ws_kernel's 128-column wave tiles fill the same records, see its file)
   const float* c1_x;
   int c1_T, c1_F;
   float* c1_part;
@@ -809,6 +817,30 @@ __device__ __forceinline__ void store_spec_tiles(const GemmArgs& g, int z, int m
 }
 // EPI_C1FOLD records per block: C1NT column tiles (N <= 512 at 128-wide tiles)
 constexpr int C1NT = 4;
+// EPI_C1FOLD's reduce-scatter of a lane's 40 sums over the 8 lanes sharing its columns: lane bit 5 (h) keeps sums
+// [20 h, 20 h + 20), bit 1 [10 b1, +10) of those, bit 0 [5 b0, +5); the lane's five are added into k5[0..4]
+__device__ __forceinline__ void c1fold_scatter(const float (&a)[40], int lane, float* k5) {
+  const int h = lane >> 5, b1 = (lane >> 1) & 1, b0 = lane & 1;
+  float r20[20];
+#pragma unroll
+  for (int u = 0; u < 20; ++u) {
+    const float send = h ? a[u] : a[20 + u];
+    r20[u] = (h ? a[20 + u] : a[u]) + __shfl_xor(send, 32, 64);
+  }
+  float r10[10];
+#pragma unroll
+  for (int u = 0; u < 10; ++u) {
+    const float send = b1 ? r20[u] : r20[10 + u];
+    r10[u] = (b1 ? r20[10 + u] : r20[u]) +
+             __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0x4E, 0xF, 0xF, false));
+  }
+#pragma unroll
+  for (int u = 0; u < 5; ++u) {
+    const float send = b0 ? r10[u] : r10[5 + u];
+    k5[u] += (b0 ? r10[5 + u] : r10[u]) +
+             __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, false));
+  }
+}
 // EPI_C1FOLD: conv1's weight / bias gradient folded into the implicit conv2 input-gradient tile (the conv1-map
 // gradient dz1 itself is never stored).  Per 32-column sub-tile j a lane holds, after the quad transpose, rows
 // m (4 per 32-row tile) x columns n..n+3; dz1 = mask(bit map) * acc, and for every such value the 9 conv1
@@ -821,7 +853,7 @@ constexpr int C1NT = 4;
 template <int TM, int TN>
 __device__ __forceinline__ void store_c1fold(const GemmArgs& g, int mrow0, int ncol0, int lane, f32x16 (&acc)[TM][TN],
                                              float (&k)[5 * TN]) {
-  const int h = lane >> 5, l32 = lane & 31, b1 = (l32 >> 1) & 1, b0 = l32 & 1;
+  const int h = lane >> 5, l32 = lane & 31;
   // the lane's 8 rows decomposed once for both 32-column sub-tiles: mask-word and conv1-input addresses
   const uint32_t* wrow[TM][4];
   const float* xrow[TM][4];
@@ -865,26 +897,7 @@ __device__ __forceinline__ void store_c1fold(const GemmArgs& g, int mrow0, int n
         }
       }
     }
-    // reduce-scatter: lane bit 5 (h) keeps sums [20 h, 20 h + 20), bit 1 [10 b1, +10) of those, bit 0 [5 b0, +5)
-    float r20[20];
-#pragma unroll
-    for (int u = 0; u < 20; ++u) {
-      const float send = h ? a[u] : a[20 + u];
-      r20[u] = (h ? a[20 + u] : a[u]) + __shfl_xor(send, 32, 64);
-    }
-    float r10[10];
-#pragma unroll
-    for (int u = 0; u < 10; ++u) {
-      const float send = b1 ? r20[u] : r20[10 + u];
-      r10[u] = (b1 ? r20[10 + u] : r20[u]) +
-               __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0x4E, 0xF, 0xF, false));
-    }
-#pragma unroll
-    for (int u = 0; u < 5; ++u) {
-      const float send = b0 ? r10[u] : r10[5 + u];
-      k[5 * j + u] += (b0 ? r10[5 + u] : r10[u]) +
-                      __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, false));
-    }
+    c1fold_scatter(a, lane, &k[5 * j]);
   }
 }
 template <int TM, int TN>
@@ -2459,6 +2472,49 @@ __global__ __launch_bounds__(glds_threads(BMT), (glds_occupancy<BNT, EPI, BMT, P
 }
 
 
+// gemm_fwd_ws_kernel / gemm_dgrad_ws_kernel: a producer lane's share of an A slab (128 rows x 32 k): 8 lanes cover a
+// row's 32 k (128 bytes), a wave 8 rows per load, the four waves 32; load i takes rows 32 i + rl.
+// pl_kc_swz(rl + 32 i) == pl_kc_swz(rl), so the lane's byte offset in a plane image advances by 32 rows per load.
+constexpr int FW_PLA = FWD_WS_BM * 64;  // bytes of one A plane image
+template <bool GA>
+struct FwStageA {
+  static constexpr int NI = FWD_WS_BM / 32;
+  int rl, kq;    // tile row of load 0; k offset of the lane's quad inside a slab
+  uint32_t lds;  // byte offset of the lane's 8 bytes of row rl in a plane image
+  __device__ __forceinline__ void init_lane(int pw, int lane) {
+    const int qd = lane & 7;
+    rl = 8 * pw + (lane >> 3);
+    kq = 4 * qd;
+    lds = (uint32_t)(rl * 64 + (((qd >> 1) ^ pl_kc_swz(rl)) << 4) + 8 * (qd & 1));
+  }
+  // the slab's tap and channel offset (GA; k0 % 32 == 0 and C % 32 == 0: a slab lies inside one tap)
+  __device__ __forceinline__ long tap_off(const GemmArgs& g, const GldsArgs& x, int k0) const {
+    const int t = (int)fdiv((uint32_t)k0, x.c_a), kt = t / 3, kf = t - 3 * kt;
+    return ((long)kt * g.a.ic.W + kf) * g.a.ic.C + (k0 - t * g.a.ic.C);
+  }
+  // load i of the slab at k0 of the tile at row m0 (rows past M read the last row; KC: quads past K the last quad)
+  __device__ __forceinline__ float4 load(const GemmArgs& g, const GldsArgs& x, int m0, int k0, long tap, int i) const {
+    const int m = min(m0 + rl + 32 * i, g.M - 1);
+    if constexpr (GA) {
+      const float* p = g.a.p + tap + kq;
+      return *reinterpret_cast<const float4*>(p + i2c_pix_off24(g.a.ic, x.hw_a, x.wo_a, (uint32_t)m));
+    } else {
+      return *reinterpret_cast<const float4*>(g.a.p + (long)m * g.a.ld + min(k0 + kq, g.K - 4));
+    }
+  }
+  // split load i's quad and write the planes; quads at k >= kv are written as zeros
+  __device__ __forceinline__ void store(float4 w, int i, char* planes, int kv) const {
+    if (!GA && kq >= kv) w = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint32_t h0, m0, l0, h1, m1, l1;
+    esp::split3_pair<false>(w.x, w.y, h0, m0, l0);
+    esp::split3_pair<false>(w.z, w.w, h1, m1, l1);
+    char* d = planes + lds + i * 32 * 64;
+    *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
+    *reinterpret_cast<uint2*>(d + FW_PLA) = make_uint2(m0, m1);
+    *reinterpret_cast<uint2*>(d + 2 * FW_PLA) = make_uint2(l0, l1);
+  }
+};
+
 // Map run-time (mode_a, mode_b, tile width, precision) onto compile-time constants for the mode
 // pairs the host issues; calls f(MA, MB, BNT, PREC) with std::integral_constant arguments.
 // false: no such instantiation.
@@ -2546,6 +2602,9 @@ bool wgrad_ws_launch(bool gather_b, bool rs, dim3 grid, hipStream_t st, const Ge
 // gemm_fwd_ws.hip: the launch of gemm_fwd_ws_kernel (g.ws == 2; false: not built, ESP_FWD_WS=0, or no such kind);
 // gather_a: A is an I2C_KC operand (x.c_a / hw_a / wo_a set), else KC; epi: EPI_BRELU or (KC only) EPI_BDR
 bool fwd_ws_launch(bool gather_a, int epi, dim3 grid, hipStream_t st, const GemmArgs& g, const GldsArgs& x);
+// gemm_dgrad_ws.hip: the launch of gemm_dgrad_ws_kernel (g.ws == 3; false: not built, ESP_DGRAD_WS=0, or no such
+// kind); epi: EPI_RMASKMAP or EPI_C1FOLD; x: the transposed-conv gather parameters with c_a = the channel count
+bool dgrad_ws_launch(int epi, dim3 grid, hipStream_t st, const GemmArgs& g, const GldsArgs& x);
 // an I2C_RC operand's pixel offsets fit i2c_pix_off24: Bn * H * W < 2^24 and the map < 2^32 elements (kpix: the
 // number of output pixels)
 inline bool i2c_rc_off24_ok(const Im2col& ic, long kpix) {

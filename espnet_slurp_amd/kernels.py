@@ -888,6 +888,22 @@ def fwd_ws_launches() -> int:
     return int(_native.load().esp_get_fwd_ws_launches())
 
 
+def set_dgrad_ws(mode: int) -> int:
+    """Kernel of the conv2 input gradient's parity-class GEMMs on the fp32 split path with the bit-map mask
+    (esp_set_dgrad_ws): 0 the LDS-DMA kernel, 1 (default) the warp-specialised kernel for the classes that measured
+    faster, 2 wherever it is eligible (D % 256 == 0, D <= 512).  Returns the previous mode."""
+    lib = _native.load()
+    prev = lib.esp_set_dgrad_ws(int(mode))
+    if prev < 0:
+        raise _native.NativeError(f"esp_set_dgrad_ws failed: {lib.esp_last_error().decode()}")
+    return prev
+
+
+def dgrad_ws_launches() -> int:
+    """Launches of gemm_dgrad_ws_kernel by this process so far (esp_get_dgrad_ws_launches)."""
+    return int(_native.load().esp_get_dgrad_ws_launches())
+
+
 def get_gemm_compute() -> int:
     return _native.load().esp_get_gemm_compute()
 

@@ -94,6 +94,18 @@ int esp_set_wgrad_ws(int mode);
 int esp_set_fwd_ws(int mode);
 /* Launches of that kernel by this process so far (tests: which kernel a call took). */
 long esp_get_fwd_ws_launches(void);
+/* (An addition to ABI 42.)  The kernel of the conv2 input gradient's four parity-class GEMMs (esp_conv2_dgrad_bits,
+ * esp_conv2_dgrad_c1fold) on the fp32 split path (fp32 dz2, fp32 compute type) of every later call (process-wide):
+ * 1 (default) = the warp-specialised kernel (csrc/gemm_dgrad_ws.hip: 128 x 256 tiles, dz2 gathered and split once per
+ * block on producer waves) for the classes that measured faster (by K = taps * D, see conv2_dgrad_impl) when the
+ * class has >= 4 rounds of 128-row tiles over the CUs; 2 = that kernel for every structurally eligible class launch
+ * (D % 256 == 0, D <= 512, B * Ha * We and B * T2 * F2 < 2^24, dz2 < 2^32 elements); 0 = never (the LDS-DMA kernel, as in a build with ESP_DGRAD_WS=0, where
+ * this call changes nothing).  Both kernels give the same dz1 bit for bit; the folded dW / db differ in the order of
+ * the per-block sums only.  esp_conv2_dgrad (fp32 mask map) and the bf16 forms are not affected.  Returns the previous
+ * mode. */
+int esp_set_dgrad_ws(int mode);
+/* Launches of that kernel by this process so far: one per class GEMM it took (tests). */
+long esp_get_dgrad_ws_launches(void);
 /* esp_gemm_f32 with B also given as its three bf16 split planes (esp_f32_to_planes of the fp32 B,
  * b = hi + mid + lo exactly): the same fp32 split products as esp_gemm_f32 on the fp32 B, in the same
  * order, bit for bit (split-K counts may differ: a different tile width), without splitting B in the

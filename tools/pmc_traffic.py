@@ -31,7 +31,7 @@ def main():
     # the fp32 / bf16-in-LDS and the bf16-operand GEMMs are all the first template; the weight gradients with the
     # operand split on producer waves (Linear and conv2) are the second, the long-K forward GEMMs with A split on
     # producer waves (conv2, FFN w_2) the third
-    fams = ("gemm_glds_kernel", "gemm_wgrad_ws_kernel", "gemm_fwd_ws_kernel")
+    fams = ("gemm_glds_kernel", "gemm_wgrad_ws_kernel", "gemm_fwd_ws_kernel", "gemm_dgrad_ws_kernel")
     fam = " + ".join(fams)
     fk = [v for n, v in fetch.values() if any(f in n for f in fams)]
     wk = [v for n, v in write.values() if any(f in n for f in fams)]

@@ -50,7 +50,7 @@ def main():
     # the bench's roofline kernel: every instantiation of the MFMA GEMM family together
     # (gemm_wgrad_ws_kernel / gemm_fwd_ws_kernel: the weight gradients / the long-K forward GEMMs with the operand
     # split on producer waves)
-    fams = ("gemm_glds_kernel", "gemm_wgrad_ws_kernel", "gemm_fwd_ws_kernel")
+    fams = ("gemm_glds_kernel", "gemm_wgrad_ws_kernel", "gemm_fwd_ws_kernel", "gemm_dgrad_ws_kernel")
     fam = [(n, t) for k, (n, t) in tot.items() if any(f in k for f in fams)]
     red = [(n, t) for k, (n, t) in tot.items() if "splitk_reduce" in k]
     if fam:
